@@ -4,7 +4,7 @@ cd /root/repo
 mkdir -p gpurun_out
 {
 echo "=== bench (driver contract, 50 steps)"
-timeout 600 python bench.py --steps 50 --warmup 5 2>&1 | tail -1
+timeout 600 python bench.py --steps 50 --warmup 5 --full 2>&1 | tail -1
 echo "=== gmg 2047^2 / 4095^2 / diffusion"
 timeout 600 python examples/gmg.py -k 11 2>&1 | grep solve:
 timeout 600 python examples/gmg.py -k 12 2>&1 | grep solve:

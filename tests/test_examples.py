@@ -86,6 +86,57 @@ def test_bench_contract():
     assert d["scaling"] == "weak"
 
 
+def _bench(*args):
+    import json
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"),
+                        "--nx", "96", "--steps", "3", "--warmup", "1",
+                        "--inner", "2", *args],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+_SECONDARY_KEYS = ("spgemm_nnz_per_s", "spgemm_ms_per_iter",
+                   "spgemm_out_nnz", "cg_ms_per_iter", "cg_gflops")
+
+
+def test_bench_dump_outputs(tmp_path):
+    """A plain run reports only the headline; --dump-outputs writes the
+    last step's y, identical from run to run and equal to A @ x."""
+    import numpy as np
+    import scipy.sparse as sp
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        res = _bench("--dump-outputs", str(d))
+        assert res["steps"] == 3 and res["ms_per_step"] > 0
+        for key in _SECONDARY_KEYS:
+            assert key not in res["config"], key
+        assert sorted(p.name for p in d.iterdir()) == ["y.npy"]
+    ya, yb = (np.load(d / "y.npy") for d in dirs)
+    assert ya.dtype == np.float64 and ya.shape == (96 * 96,)
+    assert np.array_equal(ya, yb)
+    # y = A @ x with x in [0, 1): the 5-pt operator bounds |y| by 8 and
+    # a random x cannot give the zero vector
+    assert np.all(np.isfinite(ya)) and np.abs(ya).max() <= 8.0
+    assert np.abs(ya).max() > 0
+    T = sp.diags([-1.0, 2.0, -1.0], [-1, 0, 1], shape=(96, 96))
+    L = sp.kronsum(T, T).tocsr()
+    # A is symmetric positive definite, so x is recoverable from y: the
+    # dump really is the product of the operator with some x in [0, 1)
+    from scipy.sparse.linalg import spsolve
+    x = spsolve(L.tocsc(), ya)
+    assert x.min() > -1e-9 and x.max() < 1 + 1e-9
+
+
+def test_bench_full_reports_secondary_sections():
+    res = _bench("--full", "--spgemm-iters", "1")
+    for key in _SECONDARY_KEYS:
+        assert key in res["config"], key
+    assert res["config"]["spgemm_out_nnz"] > res["config"]["nnz"]
+
+
 @pytest.mark.gpu
 def test_pde_gpu():
     import torch
