@@ -28,7 +28,7 @@ import torch
 
 import warnings
 
-from . import comm, ops
+from . import _cext, comm, ops
 from .base import CompressedBase, as_torch_1d
 from .lsarray import lsarray
 from .runtime import runtime
@@ -120,6 +120,31 @@ def _assemble_local_rows(row_local, col, val, lr, N, dedup=True):
     return indptr, col, val
 
 
+class _AffinePlan(tuple):
+    """(nd, D int32, mask uint8, rest rows, xconsec), plus the per-tile
+    table ``tile_base`` carried as an attribute so the 5-field shape the
+    callers unpack stays what it was."""
+    tile_base = None
+
+
+def _affine_tile_table(indptr: torch.Tensor, mask: torch.Tensor,
+                       tile: int) -> torch.Tensor:
+    """int64[ceil(n / tile)]: indptr[t*tile] where all ``tile`` rows of
+    tile t exist and conform (mask == 1), else -1.  Inside such a tile
+    row r starts at tile_base[t] + (r - t*tile) * nd, so the kernel
+    reads neither indptr nor mask there."""
+    n = mask.numel()
+    n_full = n // tile
+    tb = torch.full(((n + tile - 1) // tile,), -1, dtype=torch.int64,
+                    device=mask.device)
+    if n_full:
+        full = mask[:n_full * tile].view(n_full, tile).min(dim=1).values
+        tb[:n_full] = torch.where(full != 0,
+                                  indptr[0:n_full * tile:tile],
+                                  tb[:n_full])
+    return tb
+
+
 def _build_affine_plan(indptr: torch.Tensor, indices: torch.Tensor,
                        max_extent: int):
     """Detect the affine-stencil structure of a LOCAL CSR block: rows
@@ -128,9 +153,10 @@ def _build_affine_plan(indptr: torch.Tensor, indices: torch.Tensor,
     in the distributed path).  Such rows never read the index stream in
     SpMV — 8 B/nnz instead of 12 B/nnz on the memory-bound path (the
     DIA-style structural specialization the CSR format hides).  Returns
-    (nd, D int32, mask uint8, rest rows, xconsec) or None; exception
-    rows (grid boundaries) go through the general gather kernel from
-    the ``rest`` list."""
+    (nd, D int32, mask uint8, rest rows, xconsec) or None, with the
+    per-tile table ``.tile_base`` (see _affine_tile_table) attached for
+    device tensors; exception rows (grid boundaries) go through the
+    general gather kernel from the ``rest`` list."""
     ip, ix = indptr, indices
     n = ip.numel() - 1
     dev = ix.device
@@ -162,8 +188,13 @@ def _build_affine_plan(indptr: torch.Tensor, indices: torch.Tensor,
         return None
     rest = torch.nonzero(mask == 0).reshape(-1)
     xconsec = bool((D == (torch.arange(nd, device=dev) + D[0])).all())
-    return (nd, D.to(torch.int32).contiguous(), mask, rest.contiguous(),
-            xconsec)
+    plan = _AffinePlan((nd, D.to(torch.int32).contiguous(), mask,
+                        rest.contiguous(), xconsec))
+    if mask.is_cuda and _cext.has_hip():
+        # the tile size is the kernel's: read it from the extension
+        plan.tile_base = _affine_tile_table(
+            ip, mask, _cext.hip_kernels.AFFINE_TILE)
+    return plan
 
 
 import scipy.sparse as _scipy_sparse

@@ -59,9 +59,10 @@ def spmv(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
     realized as an adjusted base pointer, the same "fake offset dense
     pointer" trick the reference plays on cuSPARSE (spmv.cu:75-90).
 
-    ``affine``: (nd, D, mask, rest) stencil plan (csr._affine_plan) —
-    rows with columns == row + D[j] skip the index stream entirely
-    (8 B/nnz instead of 12 B/nnz); exception rows run from a row list.
+    ``affine``: stencil plan (csr._affine_plan) — rows with columns ==
+    row + D[j] skip the index stream entirely (8 B/nnz instead of
+    12 B/nnz), and whole tiles of such rows skip indptr and the mask as
+    well (plan.tile_base); exception rows run from a row list.
     """
     n_rows = indptr.numel() - 1
     if y is None:
@@ -71,10 +72,15 @@ def spmv(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
     if _use_hip(vals):
         ext = _cext.require_hip()
         if affine is not None and pair < 0 and w_override == 0:
-            nd, D, mask, rest, xconsec = affine
+            nd, D, mask, rest, xconsec = affine[:5]
             import os as _os
             v2 = _os.environ.get("LS_SPMV_AFFINE_V", "1") == "2" and \
                 not vals.is_complex()
+            # LS_SPMV_AFFINE_TILES=0: null tile table, every tile takes
+            # the per-row (mixed) path — in-build A/B of the tile table
+            tiles = (getattr(affine, "tile_base", None)
+                     if _os.environ.get("LS_SPMV_AFFINE_TILES", "1") != "0"
+                     else None)
             fuse_dot = (dot_out is not None and not accumulate
                         and not v2 and not vals.is_complex())
             if fuse_dot and rest.numel():
@@ -98,6 +104,7 @@ def spmv(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
                 ext.spmv_affine(indptr.data_ptr(), vals.data_ptr(), x_ptr,
                                 y.data_ptr(), D.data_ptr(),
                                 mask.data_ptr(),
+                                tiles.data_ptr() if tiles is not None else 0,
                                 n_rows, int(nd), _code(vals), accumulate,
                                 dot_out.data_ptr() if fuse_dot else 0,
                                 _stream())

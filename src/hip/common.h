@@ -15,6 +15,9 @@
 
 #define WAVE_SIZE 64
 #define LS_THREADS 256
+// rows per entry of the affine SpMV plan's tile table (one wave); the
+// extension exports it as AFFINE_TILE so the plan builder cannot drift
+#define LS_AFFINE_TILE 64
 
 // Debug bounds checking (build with LS_DEBUG=1 -> -DLS_BOUNDS_CHECK):
 // aborts the kernel with a device-side trap on an out-of-range index —

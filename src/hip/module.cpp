@@ -14,7 +14,9 @@ using i64 = int64_t;
 void ls_spmv(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, i64,
              i64, int, int, bool, uintptr_t, int, bool, int, int, i64);
 void ls_spmv_affine(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
-                    uintptr_t, i64, int, int, bool, uintptr_t, uintptr_t);
+                    uintptr_t, uintptr_t, i64, int, int, bool, uintptr_t,
+                    uintptr_t);
+int ls_affine_tile();
 void ls_spmv_rows(uintptr_t, i64, uintptr_t, uintptr_t, uintptr_t,
                   uintptr_t, uintptr_t, int, int, bool, uintptr_t);
 void ls_cg_fused(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
@@ -96,6 +98,7 @@ PYBIND11_MODULE(_hip_kernels, m) {
   m.doc() = "legate_sparse gfx950 HIP kernels";
   m.def("spmv", &ls_spmv);
   m.def("spmv_affine", &ls_spmv_affine);
+  m.attr("AFFINE_TILE") = ls_affine_tile();
   m.def("spmv_rows", &ls_spmv_rows);
   m.def("cg_fused", &ls_cg_fused);
   m.def("gs_dots", &ls_gs_dots);

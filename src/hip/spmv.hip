@@ -371,27 +371,51 @@ __global__ __launch_bounds__(LS_THREADS) void spmv_stream_kernel(
 // and cached host-side — 5-pt stencils, banded operators) never load
 // the index stream at all: 8 B/nnz instead of 12 B/nnz on the
 // memory-bound path.  Non-conforming rows (grid boundaries, ~0.1%) are
-// masked out here and computed by spmv_rows_kernel from a row list.
+// masked out here and computed by spmv_rows_kernel from a row list:
+// run inline, one lane's serial indptr/indices/x chain holds its whole
+// wave for ~10 memory latencies (measured +30 us on Poisson 4096^2,
+// profiles/spmv_affine_tiles.md).
+//
+// Each wave walks tiles of LS_AFFINE_TILE rows.  tile_base[t] >= 0 says
+// every row of tile t conforms, so row r of it starts at
+// tile_base[t] + (r - t*TILE) * ND: neither indptr nor mask is read
+// (one uniform 8-B load per wave instead of 9 B per row).  A tile with
+// tile_base[t] < 0 (or a null table) is mixed: its conforming rows read
+// mask + indptr per row.
 template <typename T, int ND, bool DOT>
 __global__ __launch_bounds__(LS_THREADS) void spmv_affine_kernel(
     const i64* __restrict__ indptr, const T* __restrict__ vals,
     const T* __restrict__ x, T* __restrict__ y,
     const int* __restrict__ D, const unsigned char* __restrict__ mask,
-    i64 n_rows, int accumulate, T* __restrict__ dot_out) {
+    const i64* __restrict__ tile_base, i64 n_rows, int accumulate,
+    T* __restrict__ dot_out) {
   // DOT: additionally reduce sum_i x[i]*y[i] into dot_out (the CG
   // pipeline's p.(A p), fused so the dot costs no extra pass)
+  static_assert(LS_AFFINE_TILE == WAVE_SIZE, "one tile per wave step");
   int d[ND];
 #pragma unroll
   for (int j = 0; j < ND; ++j) d[j] = D[j];  // uniform: lands in sgprs
-  const i64 stride = (i64)gridDim.x * blockDim.x;
+  const int lane = threadIdx.x % WAVE_SIZE;
+  // wave-uniform tile index, kept scalar so the table load is scalar
+  const i64 wave0 = __builtin_amdgcn_readfirstlane(
+      (int)((blockIdx.x * blockDim.x + threadIdx.x) / WAVE_SIZE));
+  const i64 n_waves = (i64)gridDim.x * (LS_THREADS / WAVE_SIZE);
+  const i64 n_tiles = (n_rows + LS_AFFINE_TILE - 1) / LS_AFFINE_TILE;
   T dacc = ls_zero<T>();
-  for (i64 row = (i64)blockIdx.x * blockDim.x + threadIdx.x; row < n_rows;
-       row += stride) {
-    if (!mask[row]) {
-      if constexpr (DOT) dacc += x[row] * y[row];
-      continue;
+  for (i64 tile = wave0; tile < n_tiles; tile += n_waves) {
+    const i64 row = tile * LS_AFFINE_TILE + lane;
+    const i64 base = tile_base ? tile_base[tile] : (i64)-1;
+    i64 s;
+    if (base >= 0) {
+      s = base + (i64)lane * ND;
+    } else {
+      if (row >= n_rows) continue;
+      if (!mask[row]) {
+        if constexpr (DOT) dacc += x[row] * y[row];
+        continue;
+      }
+      s = indptr[row];
     }
-    const i64 s = indptr[row];
     T v[ND], xv[ND];
 #pragma unroll
     for (int j = 0; j < ND; ++j) v[j] = vals[s + j];
@@ -658,20 +682,29 @@ namespace {
 template <typename T>
 void spmv_affine_dispatch_nd(const i64* indptr, const T* vals, const T* x,
                              T* y, const int* D,
-                             const unsigned char* mask, i64 n_rows, int nd,
+                             const unsigned char* mask,
+                             const i64* tile_base, i64 n_rows, int nd,
                              int accumulate, T* dot_out, hipStream_t s) {
-  const int grid = grid_1d(n_rows, LS_THREADS, 8192);
+  // one tile per wave, blocks dispatched in row order: measured 162.6 us
+  // uncapped vs 168.6 / 174.6 / 182.9 us at caps 32768 / 16384 / 8192
+  // (Poisson 4096^2, profiles/spmv_affine_tiles.md); the grid-stride
+  // loop only runs past 2^30 rows.  The DOT variant keeps the 8192 cap:
+  // every block ends in one atomic on dot_out.
+  const char* gcap_env = std::getenv("LS_SPMV_AFFINE_GRID");
+  int gcap = gcap_env ? atoi(gcap_env) : 0;
+  if (gcap < 1) gcap = dot_out ? 8192 : 1 << 22;
+  const int grid = grid_1d(n_rows, LS_THREADS, gcap);
   switch (nd) {
 #define LS_AFF_CASE(N)                                                     \
   case N:                                                                  \
     if (dot_out)                                                           \
       hipLaunchKernelGGL((spmv_affine_kernel<T, N, true>), dim3(grid),     \
                          dim3(LS_THREADS), 0, s, indptr, vals, x, y, D,    \
-                         mask, n_rows, accumulate, dot_out);               \
+                         mask, tile_base, n_rows, accumulate, dot_out);    \
     else                                                                   \
       hipLaunchKernelGGL((spmv_affine_kernel<T, N, false>), dim3(grid),    \
                          dim3(LS_THREADS), 0, s, indptr, vals, x, y, D,    \
-                         mask, n_rows, accumulate, dot_out);               \
+                         mask, tile_base, n_rows, accumulate, dot_out);    \
     break;
     LS_AFF_CASE(1)
     LS_AFF_CASE(2) LS_AFF_CASE(3) LS_AFF_CASE(4) LS_AFF_CASE(5)
@@ -745,9 +778,9 @@ void ls_spmv_affine2(uintptr_t indptr, uintptr_t vals, uintptr_t x,
 }
 
 void ls_spmv_affine(uintptr_t indptr, uintptr_t vals, uintptr_t x,
-                    uintptr_t y, uintptr_t D, uintptr_t mask, i64 n_rows,
-                    int nd, int dtype, bool accumulate, uintptr_t dot_out,
-                    uintptr_t stream) {
+                    uintptr_t y, uintptr_t D, uintptr_t mask,
+                    uintptr_t tile_base, i64 n_rows, int nd, int dtype,
+                    bool accumulate, uintptr_t dot_out, uintptr_t stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (dot_out && dtype > 1)
     throw std::runtime_error("spmv_affine dot fusion: real dtypes only");
@@ -756,9 +789,12 @@ void ls_spmv_affine(uintptr_t indptr, uintptr_t vals, uintptr_t x,
       reinterpret_cast<const val_t*>(vals),
       reinterpret_cast<const val_t*>(x), reinterpret_cast<val_t*>(y),
       reinterpret_cast<const int*>(D),
-      reinterpret_cast<const unsigned char*>(mask), n_rows, nd,
+      reinterpret_cast<const unsigned char*>(mask),
+      reinterpret_cast<const i64*>(tile_base), n_rows, nd,
       accumulate ? 1 : 0, reinterpret_cast<val_t*>(dot_out), s));
 }
+
+int ls_affine_tile() { return LS_AFFINE_TILE; }
 
 void ls_spmv_rows(uintptr_t rows_list, i64 n_list, uintptr_t indptr,
                   uintptr_t indices, uintptr_t vals, uintptr_t x,
