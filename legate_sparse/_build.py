@@ -56,6 +56,7 @@ def build_cpu(force: bool = False) -> str:
 HIP_SOURCES = [
     os.path.join(SRC_DIR, "hip", "module.cpp"),
     os.path.join(SRC_DIR, "hip", "spmv.hip"),
+    os.path.join(SRC_DIR, "hip", "spmm.hip"),
     os.path.join(SRC_DIR, "hip", "spgemm.hip"),
     os.path.join(SRC_DIR, "hip", "convert.hip"),
     os.path.join(SRC_DIR, "hip", "solver_ops.hip"),

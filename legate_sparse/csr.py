@@ -829,6 +829,139 @@ class csr_array(CompressedBase):
         y = lsarray.wrap(y.reshape(-1, 1) if squeezed else y, self._shape[0])
         return y
 
+    def _coerce_mat(self, other) -> torch.Tensor:
+        """2-D operand -> row-major tensor on the data's device."""
+        copied = False
+        if isinstance(other, torch.Tensor):
+            t = other
+        else:
+            a = np.asarray(other)
+            if a.ndim == 2 and any(s < 0 for s in a.strides):
+                # torch cannot view negative strides: numpy makes the copy
+                a = np.ascontiguousarray(a)
+                copied = True
+            t = torch.from_numpy(a)
+        if t.ndim != 2:
+            raise ValueError(
+                f"matmat expects a 2-D operand, got {t.ndim}-D")
+        if copied or not t.is_contiguous():
+            warnings.warn(
+                "implicit copy of a non-contiguous operand block; pass a "
+                "row-major contiguous tensor to avoid the copy",
+                RuntimeWarning)
+        return t.to(self._data.device).contiguous()
+
+    def _matmat_dist(self, X: torch.Tensor,
+                     Y: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Distributed SpMM on a local (shard_rows, k) block of X: the
+        block analogue of ``_matvec_dist``.  Row-major row ranges are
+        contiguous, so the vector exchange carries over with every count
+        multiplied by k; the cached halo plan and interior/halo split are
+        reused as they are."""
+        from .settings import settings as _settings
+        k = int(X.shape[1])
+        N = self._shape[1]
+        part = runtime.partition(N)
+        if not _settings.precise_images:
+            x_full = comm.allgatherv(X.reshape(-1),
+                                     [c * k for c in part.counts()])
+            return ops.spmm(self._indptr, self._indices, self._data,
+                            x_full.reshape(N, k), Y)
+        lo = part.lo(runtime.rank)
+        # collective on first build: reached by every rank before any
+        # rank-local early-out, and all ranks branch on the GLOBAL
+        # any_halo flag (see _matvec_dist)
+        plan = self._halo_plan()
+        if not plan["any_halo"]:
+            return ops.spmm(self._indptr, self._indices, self._data, X, Y,
+                            col_offset=lo)
+        ((ip_i, ix_i, dv_i, _),
+         (ip_h, ix_h, dv_h, _), _) = self._split_for_overlap()
+        pieces = [X[s:s + c].reshape(-1) for (s, c) in plan["send"]
+                  if c > 0]
+        send = torch.cat(pieces) if pieces else X.reshape(-1)[:0]
+        x_win, work = comm.alltoallv_single_async(
+            send, [c * k for (_, c) in plan["send"]],
+            [c * k for c in plan["recv_counts"]])
+        Y = ops.spmm(ip_i, ix_i, dv_i, X, Y, col_offset=lo)
+        if work is not None:
+            work.wait()
+        if ix_h.numel():
+            ops.spmm(ip_h, ix_h, dv_h, x_win.reshape(plan["win"], k), Y,
+                     accumulate=True, col_offset=plan["min_col"])
+        return Y
+
+    def matmat(self, X, out=None):
+        """``Y = A @ X`` for a dense block ``X`` of shape (N, k) or this
+        rank's (shard_rows, k) block of it; returns this rank's
+        (local_rows, k) block, row-major.  One pass over the matrix for
+        all k columns.  (``dot``/``@`` still reject 2-D dense operands;
+        routing them here is a follow-up.)"""
+        t = X if isinstance(X, torch.Tensor) else np.asarray(X)
+        if t.ndim != 2:
+            raise ValueError(f"matmat expects a 2-D operand, got {t.ndim}-D")
+        if isinstance(t, torch.Tensor):
+            tdt = t.dtype
+        elif t.dtype.kind in "fc":
+            tdt = torch.from_numpy(np.empty(0, dtype=t.dtype)).dtype
+        else:
+            tdt = None
+        if tdt is None or not (tdt.is_floating_point or tdt.is_complex):
+            raise NotImplementedError(
+                f"unsupported operand dtype {t.dtype} "
+                "(float32/float64/complex64/complex128 only)")
+        dt = torch.promote_types(self._data.dtype, tdt)
+        _check_value_dtype(dt)
+        Xc = self._coerce_mat(t).to(dt)
+        A = self if self._data.dtype == dt else self.astype(
+            to_numpy_dtype(dt))
+        M, N = self._shape
+        lr = self._row_hi - self._row_lo
+        k = int(Xc.shape[1])
+        shard = runtime.partition(N).count(runtime.rank)
+        if Xc.shape[0] != N and Xc.shape[0] != shard:
+            raise ValueError(
+                f"X row count {Xc.shape[0]} is neither global ({N}) nor "
+                f"the local shard ({shard})")
+        np_out = None
+        Y = None
+        if isinstance(out, np.ndarray):
+            # host array of the GLOBAL shape, filled with the gathered
+            # result (as dot does for vectors)
+            if out.shape != (M, k) or out.dtype != to_numpy_dtype(dt):
+                raise ValueError(
+                    f"bad out= block: numpy out must be the global "
+                    f"({M}, {k}) of dtype {dt}")
+            np_out = out
+        elif out is not None:
+            if not isinstance(out, torch.Tensor) \
+                    or out.device != self._data.device \
+                    or tuple(out.shape) != (lr, k) or out.dtype != dt \
+                    or not out.is_contiguous():
+                raise ValueError(
+                    f"bad out= block: need a contiguous ({lr}, {k}) "
+                    f"{dt} tensor on {self._data.device}")
+            Y = out
+        if k == 0:
+            if np_out is not None:
+                return np_out
+            if Y is None:
+                Y = torch.empty((lr, 0), dtype=dt, device=self._data.device)
+            return lsarray.wrap(Y, M)
+        if runtime.world_size > 1 and Xc.shape[0] != N:
+            Y = A._matmat_dist(Xc, Y)
+        else:
+            # replicated X (or a single rank): global columns index X
+            # directly, no communication at any world size
+            Y = ops.spmm(A._indptr, A._indices, A._data, Xc, Y)
+        if np_out is not None:
+            full = Y if runtime.world_size == 1 else comm.allgatherv(
+                Y.reshape(-1),
+                [c * k for c in self._part.counts()]).reshape(M, k)
+            np_out[...] = full.detach().cpu().numpy()
+            return np_out
+        return lsarray.wrap(Y, M)
+
     def __matmul__(self, other):
         return self.dot(other)
 
@@ -1152,6 +1285,11 @@ def spmv(A: csr_array, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     return ops.spmv(A._indptr, A._indices, A._data, x_win, y.reshape(-1),
                     col_offset=col_off, max_nnz=A._max_row_nnz(),
                     affine=A._affine_plan() if A._data.is_cuda else None)
+
+
+def spmm(A: csr_array, X, Y: torch.Tensor) -> torch.Tensor:
+    """Y = A @ X into a preallocated local (local_rows, k) block Y."""
+    return A.matmat(X, out=Y)
 
 
 def _col_windows(A: csr_array):

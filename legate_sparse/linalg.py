@@ -121,6 +121,33 @@ class LinearOperator:
             return out
         return y
 
+    def _apply_columns(self, fn, X, n_out):
+        """Generic block product: ``fn`` column by column, stacked."""
+        if getattr(X, "ndim", None) != 2:
+            raise ValueError("expected a 2-D block of column vectors")
+        is_t = isinstance(X, torch.Tensor)
+        k = int(X.shape[1])
+        if k == 0:
+            return (X.new_empty((n_out, 0)) if is_t
+                    else np.empty((n_out, 0), dtype=X.dtype))
+        cols = []
+        for j in range(k):
+            xj = X[:, j].contiguous() if is_t \
+                else np.ascontiguousarray(X[:, j])
+            cols.append(fn(xj))
+        if all(isinstance(c, torch.Tensor) for c in cols):
+            return torch.stack([c.reshape(-1) for c in cols], dim=1)
+        return np.stack([np.asarray(c).reshape(-1) for c in cols], axis=1)
+
+    def matmat(self, X):
+        """``A @ X`` for a 2-D block X (scipy's LinearOperator.matmat);
+        subclasses with a native block product override this."""
+        return self._apply_columns(self.matvec, X, self.shape[0])
+
+    def rmatmat(self, X):
+        """``A^H @ X`` for a 2-D block X."""
+        return self._apply_columns(self.rmatvec, X, self.shape[1])
+
     def __matmul__(self, x):
         return self.matvec(x)
 
@@ -140,6 +167,14 @@ class IdentityOperator(LinearOperator):
 
     rmatvec = matvec
 
+    def matmat(self, X):
+        if getattr(X, "ndim", None) != 2:
+            raise ValueError("expected a 2-D block of column vectors")
+        return X.clone() if isinstance(X, torch.Tensor) \
+            else np.array(X, copy=True)
+
+    rmatmat = matmat
+
 
 class _SparseMatrixLinearOperator(LinearOperator):
     """Wraps a csr_array; caches A.conj().T for rmatvec
@@ -157,6 +192,14 @@ class _SparseMatrixLinearOperator(LinearOperator):
         if self._AH is None:
             self._AH = self.A.conj().transpose()
         return self._AH.dot(x, out=out)
+
+    def matmat(self, X):
+        return self.A.matmat(X)
+
+    def rmatmat(self, X):
+        if self._AH is None:
+            self._AH = self.A.conj().transpose()
+        return self._AH.matmat(X)
 
 
 def aslinearoperator(A):

@@ -5,6 +5,7 @@ from __future__ import annotations
 from .coverage import track_provenance
 from .csr import csr_array, csr_matrix  # noqa
 from .csr import spmv as _spmv, spgemm_csr_csr_csr as _spgemm
+from .csr import spmm as _spmm
 from .dia import dia_array, dia_matrix  # noqa
 from .gallery import diags as _diags, eye as _eye, identity as _identity
 from .io import mmread as _mmread, mmwrite as _mmwrite
@@ -16,6 +17,7 @@ from .types import coord_ty, nnz_ty  # noqa
 # track_provenance, coverage.py:87-107; enable ranges with
 # utils.enable_profiler_ranges())
 spmv = track_provenance(_spmv, "spmv")
+spmm = track_provenance(_spmm, "spmm")
 spgemm_csr_csr_csr = track_provenance(_spgemm, "spgemm_csr_csr_csr")
 diags = track_provenance(_diags, "diags")
 eye = track_provenance(_eye, "eye")

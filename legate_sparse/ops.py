@@ -144,6 +144,82 @@ def spmv(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# SpMM: Y[i, :] (+)= sum_j vals[jp] * X[indices[jp], :]   (X, Y row-major)
+# ---------------------------------------------------------------------------
+# the narrow/wide crossover of path="auto": k <= this takes the narrow
+# kernel (row split over a sub-wave, K accumulators per lane), larger k the
+# wide one (lanes over columns)
+SPMM_NARROW_MAX = 4
+# largest k that path="narrow" accepts: the K values the narrow kernel is
+# instantiated for (the extension exports the same number and refuses more)
+SPMM_NARROW_KMAX = 8
+
+_SPMM_PATHS = ("auto", "narrow", "wide")
+
+
+def spmm(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
+         X: torch.Tensor, Y: Optional[torch.Tensor] = None,
+         accumulate: bool = False, col_offset: int = 0,
+         path: str = "auto") -> torch.Tensor:
+    """CSR x dense block.  ``X`` is a row-major window whose row
+    ``c - col_offset`` holds global column ``c`` — an adjusted base pointer
+    as in ``spmv``, shifted by ``col_offset * k`` elements.
+
+    ``path`` forces the HIP kernel ("narrow" | "wide"); "auto" picks narrow
+    for k <= SPMM_NARROW_MAX.  It is validated on every route so a typo
+    never passes silently on CPU."""
+    if path not in _SPMM_PATHS:
+        raise ValueError(f"spmm path must be one of {_SPMM_PATHS}, "
+                         f"got {path!r}")
+    if X.ndim != 2 or not X.is_contiguous():
+        raise ValueError("spmm needs a contiguous row-major 2-D X")
+    n_rows = indptr.numel() - 1
+    k = int(X.shape[1])
+    if path == "narrow" and k > SPMM_NARROW_KMAX:
+        raise ValueError(f"spmm path 'narrow' supports k <= "
+                         f"{SPMM_NARROW_KMAX}, got k = {k}")
+    if Y is None:
+        Y = torch.empty((n_rows, k), dtype=vals.dtype, device=vals.device)
+        accumulate = False
+    elif (Y.ndim != 2 or tuple(Y.shape) != (n_rows, k)
+          or not Y.is_contiguous()):
+        raise ValueError(f"spmm needs a contiguous ({n_rows}, {k}) Y")
+    if n_rows == 0 or k == 0:
+        return Y
+    if vals.numel() == 0:
+        # nothing to gather (and X may be an empty window with no storage)
+        if not accumulate:
+            Y.zero_()
+        return Y
+    x_ptr = X.data_ptr() - int(col_offset) * k * X.element_size()
+    if _use_hip(vals):
+        ext = _cext.require_hip()
+        narrow = path == "narrow" or (path == "auto"
+                                      and k <= SPMM_NARROW_MAX)
+        ext.spmm(indptr.data_ptr(), indices.data_ptr(), vals.data_ptr(),
+                 x_ptr, Y.data_ptr(), n_rows, vals.numel(), k,
+                 int(col_offset), int(X.shape[0]), _code(vals),
+                 _icode(indices), accumulate, 0 if narrow else 1, _stream())
+        return Y
+    if not vals.is_cuda and _cext.has_cpu():
+        _cext.require_cpu().spmm(indptr.data_ptr(), indices.data_ptr(),
+                                 vals.data_ptr(), x_ptr, Y.data_ptr(),
+                                 n_rows, k, _code(vals), _icode(indices),
+                                 accumulate)
+        return Y
+    # torch fallback (debug / extension-less CPU)
+    prod = vals.unsqueeze(1) * X[(indices.long() - col_offset)]
+    row_ids = torch.repeat_interleave(
+        torch.arange(n_rows, device=vals.device),
+        (indptr[1:] - indptr[:-1]),
+    )
+    if not accumulate:
+        Y.zero_()
+    Y.index_add_(0, row_ids, prod)
+    return Y
+
+
+# ---------------------------------------------------------------------------
 # SpGEMM (local rows of A) x (gathered rows of B) -> local rows of C
 # ---------------------------------------------------------------------------
 def spgemm_local(

@@ -43,6 +43,23 @@ static void spmv_impl(const i64* indptr, const I* indices, const T* vals,
   }
 }
 
+// CSR x dense block: Y[i, :] (+)= sum_jp vals[jp] * X[indices[jp], :],
+// X and Y row-major with k columns.  Row-parallel, inner loop over k.
+template <typename T, typename I>
+static void spmm_impl(const i64* indptr, const I* indices, const T* vals,
+                      const T* x, T* y, i64 n_rows, i64 k, bool accumulate) {
+#pragma omp parallel for schedule(static) if (n_rows * k > 16384)
+  for (i64 i = 0; i < n_rows; ++i) {
+    T* yr = y + i * k;
+    if (!accumulate) std::fill(yr, yr + k, T(0));
+    for (i64 jp = indptr[i]; jp < indptr[i + 1]; ++jp) {
+      const T v = vals[jp];
+      const T* xr = x + (i64)indices[jp] * k;
+      for (i64 q = 0; q < k; ++q) yr[q] += v * xr[q];
+    }
+  }
+}
+
 // Gustavson symbolic: row_nnz[i] = |union of B-row col sets over A's row i|.
 template <typename I>
 static void spgemm_symbolic_impl(const i64* A_indptr, const I* A_indices,
@@ -142,6 +159,17 @@ static void spmv(uintptr_t indptr, uintptr_t indices, uintptr_t vals,
       reinterpret_cast<scalar_t*>(y), n_rows, accumulate))));
 }
 
+static void spmm(uintptr_t indptr, uintptr_t indices, uintptr_t vals,
+                 uintptr_t x, uintptr_t y, i64 n_rows, i64 k, int dtype,
+                 int idx_dtype, bool accumulate) {
+  DISPATCH_VAL(dtype, DISPATCH_IDX(idx_dtype, (spmm_impl<scalar_t, index_t>(
+      reinterpret_cast<const i64*>(indptr),
+      reinterpret_cast<const index_t*>(indices),
+      reinterpret_cast<const scalar_t*>(vals),
+      reinterpret_cast<const scalar_t*>(x),
+      reinterpret_cast<scalar_t*>(y), n_rows, k, accumulate))));
+}
+
 static void spgemm_symbolic(uintptr_t A_indptr, uintptr_t A_indices,
                             i64 n_rowsA, uintptr_t B_indptr,
                             uintptr_t B_indices, i64 n_colsB,
@@ -177,6 +205,9 @@ PYBIND11_MODULE(_cpu_kernels, m) {
   m.def("spmv", &spmv, py::arg("indptr"), py::arg("indices"), py::arg("vals"),
         py::arg("x"), py::arg("y"), py::arg("n_rows"), py::arg("dtype"),
         py::arg("idx_dtype"), py::arg("accumulate") = false);
+  m.def("spmm", &spmm, py::arg("indptr"), py::arg("indices"), py::arg("vals"),
+        py::arg("x"), py::arg("y"), py::arg("n_rows"), py::arg("k"),
+        py::arg("dtype"), py::arg("idx_dtype"), py::arg("accumulate") = false);
   m.def("spgemm_symbolic", &spgemm_symbolic);
   m.def("spgemm_numeric", &spgemm_numeric);
 #ifdef _OPENMP

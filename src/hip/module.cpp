@@ -17,6 +17,9 @@ void ls_spmv_affine(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
                     uintptr_t, uintptr_t, i64, int, int, bool, uintptr_t,
                     uintptr_t);
 int ls_affine_tile();
+void ls_spmm(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, i64,
+             i64, i64, i64, i64, int, int, bool, int, uintptr_t);
+int ls_spmm_narrow_kmax();
 void ls_spmv_rows(uintptr_t, i64, uintptr_t, uintptr_t, uintptr_t,
                   uintptr_t, uintptr_t, int, int, bool, uintptr_t);
 void ls_cg_fused(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
@@ -100,6 +103,8 @@ PYBIND11_MODULE(_hip_kernels, m) {
   m.def("spmv_affine", &ls_spmv_affine);
   m.attr("AFFINE_TILE") = ls_affine_tile();
   m.def("spmv_rows", &ls_spmv_rows);
+  m.def("spmm", &ls_spmm);
+  m.attr("SPMM_NARROW_KMAX") = ls_spmm_narrow_kmax();
   m.def("cg_fused", &ls_cg_fused);
   m.def("gs_dots", &ls_gs_dots);
   m.def("segsort_temp_bytes", &ls_segsort_temp_bytes);
