@@ -197,6 +197,70 @@ def _build_affine_plan(indptr: torch.Tensor, indices: torch.Tensor,
     return plan
 
 
+# a matrix whose constant-tile table went stale this many times stops
+# being scanned: an application that rewrites its coefficients every step
+# must not pay the detection pass (one read of vals) every step
+_CONST_MAX_INVALIDATIONS = 2
+
+
+class _AffineConst:
+    """Value-bound companion of an affine plan: ``tile_cbase`` marks the
+    full tiles whose every row holds the values ``C`` bit for bit with
+    -2 (the SpMV kernel then reads no value stream there).  Valid only
+    for the plan object, the values buffer and the version of its
+    contents it was built from."""
+    __slots__ = ("tile_cbase", "C", "plan", "data_ptr", "version")
+
+    def __init__(self, tile_cbase, C, plan, vals):
+        self.tile_cbase = tile_cbase
+        self.C = C
+        self.plan = plan
+        self.data_ptr = vals.data_ptr()
+        self.version = vals._version
+
+    def matches(self, plan, vals) -> bool:
+        return (self.plan is plan and self.data_ptr == vals.data_ptr()
+                and self.version == vals._version)
+
+
+def _affine_const_table(plan, vals: torch.Tensor):
+    """(tile_cbase, C) of ``vals`` under ``plan``, or None when there is
+    nothing to scan: no tile table, no full tile, a complex dtype (the
+    constant-tile kernels are instantiated for real values only) or an
+    fp32 stencil wider than the extension's AFFINE_CONST_F32_ND (past it
+    the kernel pair would not give the same bits, see spmv.hip).  C is
+    the first row of the first full tile; the scan is one native pass
+    over ``vals`` (ls_affine_const_tiles)."""
+    tb = getattr(plan, "tile_base", None) if plan is not None else None
+    if tb is None or not vals.is_cuda or vals.is_complex() \
+            or not _cext.has_hip():
+        return None
+    if vals.dtype == torch.float32 and \
+            int(plan[0]) > _cext.hip_kernels.AFFINE_CONST_F32_ND:
+        return None
+    full = torch.nonzero(tb >= 0)
+    if not full.numel():
+        return None
+    nd = int(plan[0])
+    s0 = int(tb[int(full[0])])
+    C = vals[s0:s0 + nd].clone()
+    cb = torch.empty_like(tb)
+    _cext.require_hip().affine_const_tiles(
+        vals.data_ptr(), tb.data_ptr(), C.data_ptr(), cb.data_ptr(),
+        tb.numel(), nd, ops._code(vals),
+        torch.cuda.current_stream().cuda_stream)
+    return cb, C
+
+
+def _build_affine_const(plan, vals: torch.Tensor):
+    """The constant-tile table of ``vals`` under ``plan`` as an
+    _AffineConst, or None when no tile comes out constant."""
+    res = _affine_const_table(plan, vals)
+    if res is None or not bool((res[0] == -2).any()):
+        return None
+    return _AffineConst(res[0], res[1], plan, vals)
+
+
 import scipy.sparse as _scipy_sparse
 
 from .coverage import clone_scipy_arr_kind
@@ -472,6 +536,10 @@ class csr_array(CompressedBase):
         _check_value_dtype(t.dtype)
         self._data = t.contiguous()
         self._ov_cache = None  # halo/interior split caches values
+        # the constant-tile table too; a new tensor can reuse the old
+        # one's address and version, so mark the entry stale by hand
+        if getattr(self, "_const_cache", None) is not None:
+            self._const_cache.version = -1
 
     @property
     def vals(self) -> torch.Tensor:
@@ -576,6 +644,44 @@ class csr_array(CompressedBase):
                                   max(self._shape))
         self._affine_cache = plan
         return plan
+
+    def _affine_const(self, plan=None):
+        """Cached constant-tile table (_AffineConst) of this matrix's
+        values under its affine plan, or None.  The cached table is
+        returned only while the plan object, ``data.data_ptr()`` and the
+        torch ``_version`` of ``data`` are the ones it was built from;
+        otherwise it is rebuilt.  The _CONST_MAX_INVALIDATIONS-th time a
+        change of VALUES (in-place write or ``data`` assignment under an
+        unchanged plan) makes it stale, the matrix stops being scanned;
+        a new plan (indices setter, eliminate_zeros) rebuilds without
+        counting.  LS_SPMV_AFFINE_CONST=0 (or LS_SPMV_AFFINE_TILES=0)
+        returns None."""
+        import os as _os
+        if not self._data.is_cuda or \
+                _os.environ.get("LS_SPMV_AFFINE_CONST", "1") == "0" or \
+                _os.environ.get("LS_SPMV_AFFINE_TILES", "1") == "0":
+            return None
+        if plan is None:
+            plan = self._affine_plan()
+        if plan is None:
+            return None
+        d = self._data
+        c = getattr(self, "_const_cache", None)
+        if c is not None:
+            # an _AffineConst; tile_cbase None records "no constant tile"
+            if c.matches(plan, d):
+                return c if c.tile_cbase is not None else None
+            if c.plan is plan:  # same structure: the values changed
+                self._const_invalidations = getattr(
+                    self, "_const_invalidations", 0) + 1
+        if getattr(self, "_const_invalidations", 0) \
+                >= _CONST_MAX_INVALIDATIONS:
+            self._const_cache = None
+            return None
+        table = _build_affine_const(plan, d)
+        self._const_cache = table if table is not None else \
+            _AffineConst(None, None, plan, d)
+        return table
 
     def _spgemm_cache_for(self, B: "csr_array") -> dict:
         """Per-(A,B)-structure cache for repeated products (binning +
@@ -691,7 +797,14 @@ class csr_array(CompressedBase):
                 "LS_SPMV_AFFINE", "1") not in ("0", "false"):
             plan_i = _build_affine_plan(interior[0], interior[1],
                                         max(self._shape))
-        self._ov_cache = (interior, halo, plan_i)
+        # dv_i is private to this cache and rebuilt with it, so its
+        # constant-tile table is built once here, keyed to dv_i
+        const_i = None
+        if plan_i is not None and \
+                _os.environ.get("LS_SPMV_AFFINE_CONST", "1") != "0" and \
+                _os.environ.get("LS_SPMV_AFFINE_TILES", "1") != "0":
+            const_i = _build_affine_const(plan_i, interior[2])
+        self._ov_cache = (interior, halo, plan_i, const_i)
         return self._ov_cache
 
     def _matvec_dist(self, x: torch.Tensor,
@@ -718,18 +831,20 @@ class csr_array(CompressedBase):
         plan = self._halo_plan()
         if not plan["any_halo"]:
             # no rank needs remote columns: pure local SpMV everywhere
+            aff = self._affine_plan() if self._data.is_cuda else None
             return ops.spmv(self._indptr, self._indices, self._data, x, y,
                             col_offset=lo, max_nnz=self._max_row_nnz(),
-                            affine=self._affine_plan()
-                            if self._data.is_cuda else None)
+                            affine=aff,
+                            affine_const=self._affine_const(aff))
         ((ip_i, ix_i, dv_i, mx_i),
-         (ip_h, ix_h, dv_h, mx_h), aff_i) = self._split_for_overlap()
+         (ip_h, ix_h, dv_h, mx_h), aff_i, const_i) = \
+            self._split_for_overlap()
         pieces = [x[s:s + c] for (s, c) in plan["send"] if c > 0]
         send = torch.cat(pieces) if pieces else x[:0]
         x_win, work = comm.alltoallv_single_async(
             send, [c for (_, c) in plan["send"]], plan["recv_counts"])
         y = ops.spmv(ip_i, ix_i, dv_i, x, y, col_offset=lo, max_nnz=mx_i,
-                     affine=aff_i)
+                     affine=aff_i, affine_const=const_i)
         if work is not None:
             work.wait()
         if ix_h.numel():
@@ -752,7 +867,8 @@ class csr_array(CompressedBase):
         if plan is None:
             return False
         ops.spmv(self._indptr, self._indices, self._data, p,
-                 q.reshape(-1), affine=plan, dot_out=pq_out)
+                 q.reshape(-1), affine=plan, dot_out=pq_out,
+                 affine_const=self._affine_const(plan))
         return True
 
     def _coerce_vec(self, other) -> torch.Tensor:
@@ -816,10 +932,10 @@ class csr_array(CompressedBase):
             y = A._matvec_dist(x, y)
         else:
             x_win, col_off = A._gather_x(x)
+            aff = A._affine_plan() if A._data.is_cuda else None
             y = ops.spmv(A._indptr, A._indices, A._data, x_win, y,
                          col_offset=col_off, max_nnz=A._max_row_nnz(),
-                         affine=A._affine_plan() if A._data.is_cuda
-                         else None)
+                         affine=aff, affine_const=A._affine_const(aff))
         if np_out is not None:
             full = y if runtime.world_size == 1 else comm.allgatherv(
                 y, self._part.counts())
@@ -876,7 +992,7 @@ class csr_array(CompressedBase):
             return ops.spmm(self._indptr, self._indices, self._data, X, Y,
                             col_offset=lo)
         ((ip_i, ix_i, dv_i, _),
-         (ip_h, ix_h, dv_h, _), _) = self._split_for_overlap()
+         (ip_h, ix_h, dv_h, _), _, _) = self._split_for_overlap()
         pieces = [X[s:s + c].reshape(-1) for (s, c) in plan["send"]
                   if c > 0]
         send = torch.cat(pieces) if pieces else X.reshape(-1)[:0]
@@ -1282,9 +1398,10 @@ def spmv(A: csr_array, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     if runtime.world_size > 1 and xv.numel() != A.shape[1]:
         return A._matvec_dist(xv, y.reshape(-1))
     x_win, col_off = A._gather_x(xv)
+    aff = A._affine_plan() if A._data.is_cuda else None
     return ops.spmv(A._indptr, A._indices, A._data, x_win, y.reshape(-1),
                     col_offset=col_off, max_nnz=A._max_row_nnz(),
-                    affine=A._affine_plan() if A._data.is_cuda else None)
+                    affine=aff, affine_const=A._affine_const(aff))
 
 
 def spmm(A: csr_array, X, Y: torch.Tensor) -> torch.Tensor:

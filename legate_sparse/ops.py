@@ -53,8 +53,8 @@ def spmv(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
          accumulate: bool = False, w_override: int = 0,
          nt: bool = False, pair: int = -1, swz: int = 0,
          col_offset: int = 0, max_nnz: int = -1,
-         affine=None, dot_out: Optional[torch.Tensor] = None
-         ) -> torch.Tensor:
+         affine=None, dot_out: Optional[torch.Tensor] = None,
+         affine_const=None) -> torch.Tensor:
     """col_offset: kernels read x[c - col_offset] for global column c —
     realized as an adjusted base pointer, the same "fake offset dense
     pointer" trick the reference plays on cuSPARSE (spmv.cu:75-90).
@@ -63,6 +63,14 @@ def spmv(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
     row + D[j] skip the index stream entirely (8 B/nnz instead of
     12 B/nnz), and whole tiles of such rows skip indptr and the mask as
     well (plan.tile_base); exception rows run from a row list.
+
+    ``affine_const``: constant-tile table of ``vals`` under ``affine``
+    (csr._AffineConst) -- full tiles whose rows all hold the same values
+    read no value stream.  It is used only if it was built from this
+    plan and from a tensor at ``vals.data_ptr()`` whose torch ``_version``
+    is still the recorded one; anything else is
+    ignored and the call runs as without it.  LS_SPMV_AFFINE_CONST=0
+    ignores it always (in-build A/B), and so does LS_SPMV_AFFINE_TILES=0.
     """
     n_rows = indptr.numel() - 1
     if y is None:
@@ -81,6 +89,14 @@ def spmv(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
             tiles = (getattr(affine, "tile_base", None)
                      if _os.environ.get("LS_SPMV_AFFINE_TILES", "1") != "0"
                      else None)
+            cst = affine_const
+            if cst is not None and (
+                    tiles is None or v2 or vals.is_complex()
+                    or cst.plan is not affine
+                    or cst.data_ptr != vals.data_ptr()
+                    or cst.version != vals._version
+                    or _os.environ.get("LS_SPMV_AFFINE_CONST", "1") == "0"):
+                cst = None
             fuse_dot = (dot_out is not None and not accumulate
                         and not v2 and not vals.is_complex())
             if fuse_dot and rest.numel():
@@ -104,9 +120,12 @@ def spmv(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
                 ext.spmv_affine(indptr.data_ptr(), vals.data_ptr(), x_ptr,
                                 y.data_ptr(), D.data_ptr(),
                                 mask.data_ptr(),
-                                tiles.data_ptr() if tiles is not None else 0,
+                                cst.tile_cbase.data_ptr() if cst is not None
+                                else tiles.data_ptr() if tiles is not None
+                                else 0,
                                 n_rows, int(nd), _code(vals), accumulate,
                                 dot_out.data_ptr() if fuse_dot else 0,
+                                cst.C.data_ptr() if cst is not None else 0,
                                 _stream())
             if rest.numel() and not fuse_dot:
                 ext.spmv_rows(rest.data_ptr(), rest.numel(),

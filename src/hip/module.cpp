@@ -15,8 +15,11 @@ void ls_spmv(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, i64,
              i64, int, int, bool, uintptr_t, int, bool, int, int, i64);
 void ls_spmv_affine(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
                     uintptr_t, uintptr_t, i64, int, int, bool, uintptr_t,
-                    uintptr_t);
+                    uintptr_t, uintptr_t);
+void ls_affine_const_tiles(uintptr_t, uintptr_t, uintptr_t, uintptr_t, i64,
+                           int, int, uintptr_t);
 int ls_affine_tile();
+int ls_affine_const_f32_nd();
 void ls_spmm(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, i64,
              i64, i64, i64, i64, int, int, bool, int, uintptr_t);
 int ls_spmm_narrow_kmax();
@@ -101,7 +104,9 @@ PYBIND11_MODULE(_hip_kernels, m) {
   m.doc() = "legate_sparse gfx950 HIP kernels";
   m.def("spmv", &ls_spmv);
   m.def("spmv_affine", &ls_spmv_affine);
+  m.def("affine_const_tiles", &ls_affine_const_tiles);
   m.attr("AFFINE_TILE") = ls_affine_tile();
+  m.attr("AFFINE_CONST_F32_ND") = ls_affine_const_f32_nd();
   m.def("spmv_rows", &ls_spmv_rows);
   m.def("spmm", &ls_spmm);
   m.attr("SPMM_NARROW_KMAX") = ls_spmm_narrow_kmax();

@@ -382,19 +382,67 @@ __global__ __launch_bounds__(LS_THREADS) void spmv_stream_kernel(
 // (one uniform 8-B load per wave instead of 9 B per row).  A tile with
 // tile_base[t] < 0 (or a null table) is mixed: its conforming rows read
 // mask + indptr per row.
-template <typename T, int ND, bool DOT>
+//
+// CONST (real dtypes): the table is the value-bound tile_cbase written by
+// affine_const_tiles_kernel below, which adds a third tile kind:
+//   -2   full AND every row of the tile holds the values cpat[0..ND)
+//        bit for bit (constant-coefficient stencils): no vals, indptr or
+//        mask load at all, the row is sum_j cpat[j] * x[row + D[j]] with
+//        cpat in sgprs -- about 10 B/row read instead of 50
+//   >= 0 full, values vary: as above
+//   -1   mixed: as above
+// cpat is a runtime argument and the sum keeps the order and shape of
+// the loaded-values path, so y has the same bits either way.  The table
+// belongs to one vals tensor at one version of its contents: the host
+// side (csr_array._affine_const) hands it out only while the plan object,
+// the tensor's data_ptr() and its torch _version are the ones it was
+// built from, rebuilds it otherwise, and stops scanning a matrix whose
+// table went stale twice; ops.spmv ignores a table of another data_ptr().
+// LS_SPMV_AFFINE_CONST=0 runs without the table, LS_SPMV_AFFINE_TILES=0
+// without either table (in-build A/B).  CONST = false never touches cpat
+// and compiles to what it did without the parameter.
+//
+// Same bits as the CONST = false kernel of the same matrix takes one more
+// step in fp32.  The fp64 sum compiles to one fma chain in every
+// instantiation.  The fp32 sum of the CONST = false kernels does not:
+// the vectoriser turns it into v_pk_mul_f32 plus adds, i.e. every
+// product is rounded before it is added, for ND <= LS_AFFINE_CONST_F32_ND
+// (beyond that it leaves a fused tail).  CONST = true fp32 kernels
+// therefore switch contraction off for the row sum, which is that same
+// arithmetic whatever the vectoriser then does, and are not offered past
+// that ND.  tests/test_spmv_affine_const.py compares the two kernels bit
+// for bit across ND, so a compiler that decides otherwise shows there.
+#define LS_AFFINE_CONST_F32_ND 13
+template <typename T, int ND>
+__device__ __forceinline__ T affine_row_sum_unfused(const T (&a)[ND],
+                                                    const T (&xv)[ND]) {
+#pragma clang fp contract(off)
+  T acc = ls_zero<T>();
+#pragma unroll
+  for (int j = 0; j < ND; ++j) acc += a[j] * xv[j];
+  return acc;
+}
+
+template <typename T, int ND, bool DOT, bool CONST>
 __global__ __launch_bounds__(LS_THREADS) void spmv_affine_kernel(
     const i64* __restrict__ indptr, const T* __restrict__ vals,
     const T* __restrict__ x, T* __restrict__ y,
     const int* __restrict__ D, const unsigned char* __restrict__ mask,
     const i64* __restrict__ tile_base, i64 n_rows, int accumulate,
-    T* __restrict__ dot_out) {
+    T* __restrict__ dot_out, const T* __restrict__ cpat) {
   // DOT: additionally reduce sum_i x[i]*y[i] into dot_out (the CG
   // pipeline's p.(A p), fused so the dot costs no extra pass)
   static_assert(LS_AFFINE_TILE == WAVE_SIZE, "one tile per wave step");
+  static_assert(!CONST || !is_cplx<T>::value, "CONST: real dtypes only");
+  constexpr bool UNFUSED = CONST && sizeof(T) == 4;
   int d[ND];
 #pragma unroll
   for (int j = 0; j < ND; ++j) d[j] = D[j];  // uniform: lands in sgprs
+  [[maybe_unused]] T c[ND];
+  if constexpr (CONST) {
+#pragma unroll
+    for (int j = 0; j < ND; ++j) c[j] = cpat[j];  // uniform, like d
+  }
   const int lane = threadIdx.x % WAVE_SIZE;
   // wave-uniform tile index, kept scalar so the table load is scalar
   const i64 wave0 = __builtin_amdgcn_readfirstlane(
@@ -405,6 +453,26 @@ __global__ __launch_bounds__(LS_THREADS) void spmv_affine_kernel(
   for (i64 tile = wave0; tile < n_tiles; tile += n_waves) {
     const i64 row = tile * LS_AFFINE_TILE + lane;
     const i64 base = tile_base ? tile_base[tile] : (i64)-1;
+    if constexpr (CONST) {
+      if (base == -2) {  // wave-uniform; the tile is whole, so row < n_rows
+        T xv[ND];
+#pragma unroll
+        for (int j = 0; j < ND; ++j) xv[j] = x[row + d[j]];
+        T acc = ls_zero<T>();
+        if constexpr (UNFUSED) {
+          acc = affine_row_sum_unfused<T, ND>(c, xv);
+        } else {
+#pragma unroll
+          for (int j = 0; j < ND; ++j) acc += c[j] * xv[j];
+        }
+        if (accumulate)
+          y[row] += acc;
+        else
+          y[row] = acc;
+        if constexpr (DOT) dacc += x[row] * acc;
+        continue;
+      }
+    }
     i64 s;
     if (base >= 0) {
       s = base + (i64)lane * ND;
@@ -422,8 +490,12 @@ __global__ __launch_bounds__(LS_THREADS) void spmv_affine_kernel(
 #pragma unroll
     for (int j = 0; j < ND; ++j) xv[j] = x[row + d[j]];
     T acc = ls_zero<T>();
+    if constexpr (UNFUSED) {
+      acc = affine_row_sum_unfused<T, ND>(v, xv);
+    } else {
 #pragma unroll
-    for (int j = 0; j < ND; ++j) acc += v[j] * xv[j];
+      for (int j = 0; j < ND; ++j) acc += v[j] * xv[j];
+    }
     if (accumulate)
       y[row] += acc;
     else
@@ -443,6 +515,33 @@ __global__ __launch_bounds__(LS_THREADS) void spmv_affine_kernel(
         total += partials[w];
       dot_atomic_add(dot_out, total);
     }
+  }
+}
+
+// Constant-tile detection for spmv_affine_kernel<.., CONST = true>: one
+// wave per tile, one read of vals.  tile_cbase[t] = -2 when tile t is
+// full (tile_base[t] >= 0) and each of its rows holds cpat[0..nd) bit
+// for bit, else tile_base[t].  U is the unsigned integer of the value's
+// width: an integer compare keeps -0.0 apart from 0.0 and NaN payloads
+// apart from each other, so a -2 tile cannot change a result bit.
+template <typename U>
+__global__ __launch_bounds__(LS_THREADS) void affine_const_tiles_kernel(
+    const U* __restrict__ vals, const i64* __restrict__ tile_base,
+    const U* __restrict__ cpat, i64* __restrict__ tile_cbase, i64 n_tiles,
+    int nd) {
+  const int lane = threadIdx.x % WAVE_SIZE;
+  const i64 wave0 = __builtin_amdgcn_readfirstlane(
+      (int)((blockIdx.x * blockDim.x + threadIdx.x) / WAVE_SIZE));
+  const i64 n_waves = (i64)gridDim.x * (LS_THREADS / WAVE_SIZE);
+  for (i64 tile = wave0; tile < n_tiles; tile += n_waves) {
+    const i64 base = tile_base[tile];
+    bool same = base >= 0;
+    if (same) {
+      const U* row = vals + base + (i64)lane * nd;
+      for (int j = 0; j < nd; ++j) same &= row[j] == cpat[j];
+    }
+    const bool all = __ballot(same) == ~0ull;
+    if (lane == 0) tile_cbase[tile] = all ? (i64)-2 : base;
   }
 }
 
@@ -684,7 +783,14 @@ void spmv_affine_dispatch_nd(const i64* indptr, const T* vals, const T* x,
                              T* y, const int* D,
                              const unsigned char* mask,
                              const i64* tile_base, i64 n_rows, int nd,
-                             int accumulate, T* dot_out, hipStream_t s) {
+                             int accumulate, T* dot_out, const T* cpat,
+                             hipStream_t s) {
+  // cpat != null: tile_base is the value-bound tile_cbase (-2 tiles)
+  if (cpat && (is_cplx<T>::value || !tile_base ||
+               (sizeof(T) == 4 && nd > LS_AFFINE_CONST_F32_ND)))
+    throw std::runtime_error(
+        "spmv_affine: constant tiles need a real dtype, a tile table and, "
+        "in fp32, nd <= " + std::to_string(LS_AFFINE_CONST_F32_ND));
   // one tile per wave, blocks dispatched in row order: measured 162.6 us
   // uncapped vs 168.6 / 174.6 / 182.9 us at caps 32768 / 16384 / 8192
   // (Poisson 4096^2, profiles/spmv_affine_tiles.md); the grid-stride
@@ -695,16 +801,25 @@ void spmv_affine_dispatch_nd(const i64* indptr, const T* vals, const T* x,
   if (gcap < 1) gcap = dot_out ? 8192 : 1 << 22;
   const int grid = grid_1d(n_rows, LS_THREADS, gcap);
   switch (nd) {
+#define LS_AFF_LAUNCH(N, DOT, CONST)                                       \
+  hipLaunchKernelGGL((spmv_affine_kernel<T, N, DOT, CONST>), dim3(grid),   \
+                     dim3(LS_THREADS), 0, s, indptr, vals, x, y, D, mask,  \
+                     tile_base, n_rows, accumulate, dot_out, cpat)
 #define LS_AFF_CASE(N)                                                     \
   case N:                                                                  \
+    if constexpr (!is_cplx<T>::value) {                                    \
+      if (cpat) {                                                          \
+        if (dot_out)                                                       \
+          LS_AFF_LAUNCH(N, true, true);                                    \
+        else                                                               \
+          LS_AFF_LAUNCH(N, false, true);                                   \
+        break;                                                             \
+      }                                                                    \
+    }                                                                      \
     if (dot_out)                                                           \
-      hipLaunchKernelGGL((spmv_affine_kernel<T, N, true>), dim3(grid),     \
-                         dim3(LS_THREADS), 0, s, indptr, vals, x, y, D,    \
-                         mask, tile_base, n_rows, accumulate, dot_out);    \
+      LS_AFF_LAUNCH(N, true, false);                                       \
     else                                                                   \
-      hipLaunchKernelGGL((spmv_affine_kernel<T, N, false>), dim3(grid),    \
-                         dim3(LS_THREADS), 0, s, indptr, vals, x, y, D,    \
-                         mask, tile_base, n_rows, accumulate, dot_out);    \
+      LS_AFF_LAUNCH(N, false, false);                                      \
     break;
     LS_AFF_CASE(1)
     LS_AFF_CASE(2) LS_AFF_CASE(3) LS_AFF_CASE(4) LS_AFF_CASE(5)
@@ -712,6 +827,7 @@ void spmv_affine_dispatch_nd(const i64* indptr, const T* vals, const T* x,
     LS_AFF_CASE(10) LS_AFF_CASE(11) LS_AFF_CASE(12) LS_AFF_CASE(13)
     LS_AFF_CASE(14) LS_AFF_CASE(15) LS_AFF_CASE(16)
 #undef LS_AFF_CASE
+#undef LS_AFF_LAUNCH
     default:
       throw std::runtime_error("spmv_affine: nd out of range (1..16)");
   }
@@ -780,7 +896,10 @@ void ls_spmv_affine2(uintptr_t indptr, uintptr_t vals, uintptr_t x,
 void ls_spmv_affine(uintptr_t indptr, uintptr_t vals, uintptr_t x,
                     uintptr_t y, uintptr_t D, uintptr_t mask,
                     uintptr_t tile_base, i64 n_rows, int nd, int dtype,
-                    bool accumulate, uintptr_t dot_out, uintptr_t stream) {
+                    bool accumulate, uintptr_t dot_out, uintptr_t cpat,
+                    uintptr_t stream) {
+  // cpat != 0: tile_base is a tile_cbase from ls_affine_const_tiles and
+  // cpat its nd-value pattern (device, the value dtype)
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (dot_out && dtype > 1)
     throw std::runtime_error("spmv_affine dot fusion: real dtypes only");
@@ -791,10 +910,40 @@ void ls_spmv_affine(uintptr_t indptr, uintptr_t vals, uintptr_t x,
       reinterpret_cast<const int*>(D),
       reinterpret_cast<const unsigned char*>(mask),
       reinterpret_cast<const i64*>(tile_base), n_rows, nd,
-      accumulate ? 1 : 0, reinterpret_cast<val_t*>(dot_out), s));
+      accumulate ? 1 : 0, reinterpret_cast<val_t*>(dot_out),
+      reinterpret_cast<const val_t*>(cpat), s));
+}
+
+void ls_affine_const_tiles(uintptr_t vals, uintptr_t tile_base,
+                           uintptr_t cpat, uintptr_t tile_cbase,
+                           i64 n_tiles, int nd, int dtype,
+                           uintptr_t stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (nd < 1 || nd > 16)
+    throw std::runtime_error("affine_const_tiles: nd out of range (1..16)");
+  if (n_tiles <= 0) return;
+  const int grid = grid_1d(n_tiles, LS_THREADS / WAVE_SIZE, 1 << 22);
+  const i64* tb = reinterpret_cast<const i64*>(tile_base);
+  i64* cb = reinterpret_cast<i64*>(tile_cbase);
+  if (dtype == 0)
+    hipLaunchKernelGGL((affine_const_tiles_kernel<uint32_t>), dim3(grid),
+                       dim3(LS_THREADS), 0, s,
+                       reinterpret_cast<const uint32_t*>(vals), tb,
+                       reinterpret_cast<const uint32_t*>(cpat), cb,
+                       n_tiles, nd);
+  else if (dtype == 1)
+    hipLaunchKernelGGL((affine_const_tiles_kernel<uint64_t>), dim3(grid),
+                       dim3(LS_THREADS), 0, s,
+                       reinterpret_cast<const uint64_t*>(vals), tb,
+                       reinterpret_cast<const uint64_t*>(cpat), cb,
+                       n_tiles, nd);
+  else
+    throw std::runtime_error("affine_const_tiles: real dtypes only");
+  ls_check(hipGetLastError(), "affine_const_tiles");
 }
 
 int ls_affine_tile() { return LS_AFFINE_TILE; }
+int ls_affine_const_f32_nd() { return LS_AFFINE_CONST_F32_ND; }
 
 void ls_spmv_rows(uintptr_t rows_list, i64 n_list, uintptr_t indptr,
                   uintptr_t indices, uintptr_t vals, uintptr_t x,
