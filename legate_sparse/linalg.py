@@ -1,5 +1,5 @@
 # SPDX-License-Identifier: Apache-2.0
-"""Iterative solvers: CG, GMRES, LinearOperator.
+"""Iterative solvers: CG, GMRES, BiCGSTAB, LinearOperator.
 
 Counterpart of the reference's ``legate_sparse/linalg.py`` (linalg.py:85-668).
 The key property preserved is the *async solver pipeline* (SURVEY §3.4):
@@ -564,3 +564,125 @@ def gmres(A, b, x0=None, tol=None, restart: Optional[int] = None,
         x = x + (yt.reshape(1, -1) @ V[:m]).reshape(-1)
     info = 0 if beta <= eff_atol else iters
     return _wrap_result(mx, n), info
+
+
+# ---------------------------------------------------------------------------
+# BiCGSTAB (docs/DESIGN.md §15): short recurrence for nonsymmetric systems
+# ---------------------------------------------------------------------------
+@track_provenance
+def bicgstab(A, b, x0=None, tol=None, maxiter: Optional[int] = None, M=None,
+             callback: Optional[Callable] = None, atol: float = 0.0,
+             rtol: float = 1e-5, conv_test_iters: int = 25):
+    """BiCGSTAB for general square systems (scipy.sparse.linalg.bicgstab
+    contract).  Seven vectors, two operator applications per iteration, no
+    restart.  ``M`` approximates the inverse of A and is applied as scipy
+    applies it: ``phat = M p``, ``shat = M s``.
+
+    The iteration never reads the host: alpha, omega and beta are formed
+    inside the fused kernels from 1-element device tensors with a guarded
+    division (x/0 := 0), so an iteration that runs on after r reached zero
+    between two convergence tests is a no-op.  At world size > 1 there are
+    exactly three all-reduces per iteration (rhv, [ts, tt], [rho, rr]) and
+    every loop-ending decision is taken from all-reduced values.
+
+    Returns ``(x, info)``: 0 converged; -10 rho or <rhat, v> broke down;
+    -11 omega broke down or a scalar is not finite; ``maxiter`` when the
+    iteration limit was reached.  Convergence and breakdown are tested
+    every ``conv_test_iters`` iterations and at ``maxiter``.
+    """
+    Aop = aslinearoperator(A)
+    if Aop.shape[0] != Aop.shape[1]:
+        raise ValueError(f"expected a square operator, got {Aop.shape}")
+    n = Aop.shape[0]
+    _check_rhs_shape(b, n)
+    dtype = Aop.dtype if Aop.dtype is not None else np.float64
+    device = runtime.device
+    b = _to_local_vec(b, n, dtype, device)
+    if maxiter is None:
+        maxiter = n * 10
+    Mop = M if isinstance(M, LinearOperator) else (
+        aslinearoperator(M) if M is not None
+        else IdentityOperator(Aop.shape, dtype=dtype))
+    ident_M = isinstance(Mop, IdentityOperator)
+
+    bnrm2 = float(_gnorm(b).item())
+    if bnrm2 == 0.0:
+        return _wrap_result(torch.zeros_like(b), n), 0
+    eff_atol, _ = _get_atol_rtol(bnrm2, tol, atol, rtol)
+
+    if x0 is None:
+        x = torch.zeros_like(b)
+        r = b.clone()
+    else:
+        x = _to_local_vec(x0, n, dtype, device).clone()
+        r = b - Aop.matvec(x).reshape(-1)
+
+    # ---- all buffers before the loop ---------------------------------
+    rhat = r.clone()
+    p = r.clone()
+    v = torch.empty_like(b)
+    s = torch.empty_like(b)
+    t = torch.empty_like(b)
+    # unpreconditioned: phat IS p and shat IS s (no copies)
+    phat = p if ident_M else torch.empty_like(b)
+    shat = s if ident_M else torch.empty_like(b)
+    rr0 = _gdot(r, r)                      # rho_0 = <rhat, r0> = ||r0||^2
+    # two [rho, ||r||^2] pairs that swap roles every iteration, each kept
+    # with the 1-element view of its rho
+    pair = torch.cat([rr0, rr0])
+    cur = (pair, pair[0:1])
+    pair = torch.zeros_like(pair)
+    nxt = (pair, pair[0:1])
+    rhv = torch.zeros_like(rr0)            # <rhat, v>
+    tst = torch.zeros_like(pair)           # [<t, s>, <t, t>]
+    ts, tt = tst[0:1], tst[1:2]
+    ws = runtime.world_size
+
+    def _status():
+        """One host read of the (all-reduced) scalars -> info or None."""
+        h = torch.cat([cur[0], rhv, tst]).cpu().numpy()
+        rho_h, rr_h, rhv_h, ts_h = h[0], h[1], h[2], h[3]
+        if np.sqrt(np.abs(rr_h)) <= eff_atol:
+            return 0
+        if rho_h == 0 or rhv_h == 0:
+            return -10
+        if ts_h == 0 or not np.all(np.isfinite(h)):
+            return -11
+        return None
+
+    if float(torch.sqrt(torch.abs(rr0)).item()) <= eff_atol:
+        return _wrap_result(x, n), 0
+
+    step = conv_test_iters if conv_test_iters > 0 else maxiter
+    iters = 0
+    info = maxiter
+    while iters < maxiter:
+        rho, out2 = cur[1], nxt[0]
+        if iters > 0:
+            ops.bicgstab_p(p, r, v, rho, rhv, ts, tt)
+        if not ident_M:
+            Mop.matvec(p, out=phat)
+        Aop.matvec(phat, out=v)
+        ops.vdot(rhat, v, out=rhv)
+        if ws > 1:
+            comm.allreduce_(rhv)
+        ops.bicgstab_s(s, r, v, rho, rhv)
+        if not ident_M:
+            Mop.matvec(s, out=shat)
+        Aop.matvec(shat, out=t)
+        ops.vdot2(t, s, tst)
+        if ws > 1:
+            comm.allreduce_(tst)
+        ops.bicgstab_xr(x, r, phat, shat, s, t, rhat, rho, rhv, ts, tt, out2)
+        if ws > 1:
+            comm.allreduce_(out2)
+        cur, nxt = nxt, cur
+        iters += 1
+        if callback is not None:
+            callback(x)
+        if iters % step == 0 or iters == maxiter:
+            st = _status()
+            if st is not None:
+                info = st
+                break
+    return _wrap_result(x, n), info

@@ -1030,3 +1030,111 @@ def vdot(x: torch.Tensor, y: torch.Tensor, conj: bool = True,
         out.copy_(res)
         return out
     return res
+
+
+# ---------------------------------------------------------------------------
+# BiCGSTAB primitives (docs/DESIGN.md §15).  Every scalar is a 1-element
+# device tensor; quotients use the GUARDED division  a (/) b  = a / b, but
+# exactly 0 when b is exactly 0 — formed in-kernel, never on the host.
+# ---------------------------------------------------------------------------
+def _gdiv(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Guarded a/b of 1-element tensors (torch path; no host sync)."""
+    zero = b == 0
+    q = a / torch.where(zero, torch.ones_like(b), b)
+    return torch.where(zero, torch.zeros_like(q), q)
+
+
+def _bicg_check(vecs, scalars=(), out2=None) -> None:
+    """The kernels take raw pointers: a wrong dtype, device or length would
+    be reinterpreted silently, so it is refused here."""
+    ref = vecs[0]
+    for t in vecs:
+        if (t.numel() != ref.numel() or not t.is_contiguous()
+                or t.dtype != ref.dtype or t.device != ref.device):
+            raise ValueError("BiCGSTAB ops need contiguous vectors of one "
+                             "length, dtype and device")
+    for t, want in [(a, 1) for a in scalars] + (
+            [(out2, 2)] if out2 is not None else []):
+        if (t.numel() != want or not t.is_contiguous()
+                or t.dtype != ref.dtype or t.device != ref.device):
+            raise ValueError(f"BiCGSTAB scalar buffers need {want} "
+                             "element(s) of the vectors' dtype and device")
+
+
+def bicgstab_p(p: torch.Tensor, r: torch.Tensor, v: torch.Tensor,
+               rho: torch.Tensor, rhv: torch.Tensor, ts: torch.Tensor,
+               tt: torch.Tensor) -> torch.Tensor:
+    """p <- r + beta (p - omega v) with omega = ts (/) tt and
+    beta = (rho (/) rhv) * (tt (/) ts), in place."""
+    _bicg_check((p, r, v), (rho, rhv, ts, tt))
+    if _use_hip(p):
+        _cext.require_hip().bicgstab_p(
+            p.data_ptr(), r.data_ptr(), v.data_ptr(), rho.data_ptr(),
+            rhv.data_ptr(), ts.data_ptr(), tt.data_ptr(), p.numel(),
+            _code(p), _stream())
+        return p
+    omega = _gdiv(ts, tt).reshape(())
+    beta = (_gdiv(rho, rhv) * _gdiv(tt, ts)).reshape(())
+    p.sub_(omega * v).mul_(beta).add_(r)
+    return p
+
+
+def bicgstab_s(s: torch.Tensor, r: torch.Tensor, v: torch.Tensor,
+               rho: torch.Tensor, rhv: torch.Tensor) -> torch.Tensor:
+    """s <- r - (rho (/) rhv) v."""
+    _bicg_check((s, r, v), (rho, rhv))
+    if _use_hip(s):
+        _cext.require_hip().bicgstab_s(
+            s.data_ptr(), r.data_ptr(), v.data_ptr(), rho.data_ptr(),
+            rhv.data_ptr(), s.numel(), _code(s), _stream())
+        return s
+    alpha = _gdiv(rho, rhv).reshape(())
+    torch.sub(r, alpha * v, out=s)
+    return s
+
+
+def vdot2(t: torch.Tensor, s: torch.Tensor,
+          out2: torch.Tensor) -> torch.Tensor:
+    """out2 <- [<t, s>, <t, t>] (conjugating t) in one pass over t and s.
+    ``out2`` is a 2-element tensor, zeroed here; caller all-reduces it."""
+    _bicg_check((t, s), out2=out2)
+    if _use_hip(t):
+        out2.zero_()
+        _cext.require_hip().vdot2(t.data_ptr(), s.data_ptr(),
+                                  out2.data_ptr(), t.numel(), _code(t),
+                                  _stream())
+        return out2
+    tc = t.conj() if t.is_complex() else t
+    out2[0] = (tc * s).sum()
+    out2[1] = (tc * t).sum()
+    return out2
+
+
+def bicgstab_xr(x: torch.Tensor, r: torch.Tensor, phat: torch.Tensor,
+                shat: torch.Tensor, s: torch.Tensor, t: torch.Tensor,
+                rhat: torch.Tensor, rho: torch.Tensor, rhv: torch.Tensor,
+                ts: torch.Tensor, tt: torch.Tensor,
+                out2: torch.Tensor) -> torch.Tensor:
+    """With alpha = rho (/) rhv and omega = ts (/) tt:
+    x <- x + alpha phat + omega shat;  r <- s - omega t;
+    out2 <- [<rhat, r_new>, <r_new, r_new>] in the same pass.
+    ``phat`` may alias p and ``shat`` may alias ``s``; x, r and out2 alias
+    nothing, and out2 must not alias an input scalar."""
+    _bicg_check((x, r, phat, shat, s, t, rhat), (rho, rhv, ts, tt), out2)
+    if _use_hip(x):
+        out2.zero_()
+        _cext.require_hip().bicgstab_xr(
+            x.data_ptr(), r.data_ptr(), phat.data_ptr(), shat.data_ptr(),
+            s.data_ptr(), t.data_ptr(), rhat.data_ptr(), rho.data_ptr(),
+            rhv.data_ptr(), ts.data_ptr(), tt.data_ptr(), out2.data_ptr(),
+            x.numel(), _code(x), _stream())
+        return out2
+    alpha = _gdiv(rho, rhv).reshape(())
+    omega = _gdiv(ts, tt).reshape(())
+    x.add_(alpha * phat).add_(omega * shat)
+    torch.sub(s, omega * t, out=r)
+    rc = r.conj() if r.is_complex() else r
+    hc = rhat.conj() if rhat.is_complex() else rhat
+    out2[0] = (hc * r).sum()
+    out2[1] = (rc * r).sum()
+    return out2

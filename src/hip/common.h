@@ -92,6 +92,14 @@ __device__ inline Cplx<float> ls_zero<Cplx<float>>() { return {0.f, 0.f}; }
 template <>
 __device__ inline Cplx<double> ls_zero<Cplx<double>>() { return {0., 0.}; }
 
+// exact-zero test (complex: both parts zero)
+template <typename T>
+__device__ inline bool ls_is_zero(T v) { return v == T(0); }
+template <typename T>
+__device__ inline bool ls_is_zero(Cplx<T> v) {
+  return v.re == T(0) && v.im == T(0);
+}
+
 // dtype codes shared with Python: 0=f32, 1=f64, 2=c64, 3=c128
 #define DISPATCH_VAL_T(code, CALL)                                  \
   switch (code) {                                                   \

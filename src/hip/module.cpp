@@ -7,6 +7,7 @@
 
 #include <pybind11/pybind11.h>
 #include <cstdint>
+#include <string>
 
 namespace py = pybind11;
 using i64 = int64_t;
@@ -99,6 +100,16 @@ void ls_axpby(uintptr_t, uintptr_t, uintptr_t, uintptr_t, i64, bool, bool,
 void ls_vdot(uintptr_t, uintptr_t, uintptr_t, i64, bool, int, uintptr_t);
 void ls_jacobi(uintptr_t, uintptr_t, uintptr_t, uintptr_t, double, i64,
                int, uintptr_t);
+void ls_bicgstab_p(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                   uintptr_t, uintptr_t, i64, int, uintptr_t);
+void ls_bicgstab_s(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                   i64, int, uintptr_t);
+void ls_vdot2(uintptr_t, uintptr_t, uintptr_t, i64, int, uintptr_t);
+void ls_bicgstab_xr(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                    uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                    uintptr_t, uintptr_t, i64, int, uintptr_t);
+int ls_bicgstab_grid_cap();
+int ls_bicgstab_per_block();
 
 PYBIND11_MODULE(_hip_kernels, m) {
   m.doc() = "legate_sparse gfx950 HIP kernels";
@@ -138,6 +149,16 @@ PYBIND11_MODULE(_hip_kernels, m) {
   m.def("axpby", &ls_axpby);
   m.def("vdot", &ls_vdot);
   m.def("jacobi", &ls_jacobi);
+  m.def("bicgstab_p", &ls_bicgstab_p);
+  m.def("bicgstab_s", &ls_bicgstab_s);
+  m.def("vdot2", &ls_vdot2);
+  m.def("bicgstab_xr", &ls_bicgstab_xr);
+  // the four BiCGSTAB kernels share one launch shape; exported per kernel
+  // so a test can size an input past cap * per_block
+  for (const char* k : {"BICGSTAB_P", "BICGSTAB_S", "VDOT2", "BICGSTAB_XR"}) {
+    m.attr((std::string(k) + "_GRID_CAP").c_str()) = ls_bicgstab_grid_cap();
+    m.attr((std::string(k) + "_PER_BLOCK").c_str()) = ls_bicgstab_per_block();
+  }
   m.attr("arch") = "gfx950";
   m.attr("spgemm_lds_bins") = py::make_tuple(48, 128, 1024, 4096);
 }
