@@ -71,6 +71,11 @@ def spmv(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
     is still the recorded one; anything else is
     ignored and the call runs as without it.  LS_SPMV_AFFINE_CONST=0
     ignores it always (in-build A/B), and so does LS_SPMV_AFFINE_TILES=0.
+    With the table and without dot fusion a wave takes
+    ``ext.affine_group(nd, dtype)`` tiles at a time (where that is > 1)
+    and the exception rows run inside the same launch;
+    LS_SPMV_AFFINE_GROUP=1 runs the one-tile kernel and its separate
+    row-list launch, LS_SPMV_AFFINE_FOLD=0 only the latter.
     """
     n_rows = indptr.numel() - 1
     if y is None:
@@ -99,6 +104,16 @@ def spmv(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
                 cst = None
             fuse_dot = (dot_out is not None and not accumulate
                         and not v2 and not vals.is_complex())
+            # LS_SPMV_AFFINE_GROUP=1: the one-tile-per-wave kernel instead
+            # of the tile-group kernel (in-build A/B)
+            group = 1 if _os.environ.get("LS_SPMV_AFFINE_GROUP") == "1" else 0
+            # the exception rows ride in the tile-group launch
+            # (LS_SPMV_AFFINE_FOLD=0: own launch); the fused dot needs
+            # them first and has no tile groups
+            fold = (cst is not None and not fuse_dot and not group
+                    and rest.numel() > 0
+                    and ext.affine_group(int(nd), _code(vals)) > 1
+                    and _os.environ.get("LS_SPMV_AFFINE_FOLD", "1") != "0")
             if fuse_dot and rest.numel():
                 # exception rows FIRST so the fused x.y reduction over
                 # non-mask rows reads final y values
@@ -126,8 +141,11 @@ def spmv(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
                                 n_rows, int(nd), _code(vals), accumulate,
                                 dot_out.data_ptr() if fuse_dot else 0,
                                 cst.C.data_ptr() if cst is not None else 0,
-                                _stream())
-            if rest.numel() and not fuse_dot:
+                                rest.data_ptr() if fold else 0,
+                                rest.numel() if fold else 0,
+                                indices.data_ptr() if fold else 0,
+                                _icode(indices), group, _stream())
+            if rest.numel() and not fuse_dot and not fold:
                 ext.spmv_rows(rest.data_ptr(), rest.numel(),
                               indptr.data_ptr(), indices.data_ptr(),
                               vals.data_ptr(), x_ptr, y.data_ptr(),

@@ -16,10 +16,12 @@ void ls_spmv(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, i64,
              i64, int, int, bool, uintptr_t, int, bool, int, int, i64);
 void ls_spmv_affine(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
                     uintptr_t, uintptr_t, i64, int, int, bool, uintptr_t,
-                    uintptr_t, uintptr_t);
+                    uintptr_t, uintptr_t, i64, uintptr_t, int, int,
+                    uintptr_t);
 void ls_affine_const_tiles(uintptr_t, uintptr_t, uintptr_t, uintptr_t, i64,
                            int, int, uintptr_t);
 int ls_affine_tile();
+int ls_affine_group(int, int);
 int ls_affine_const_f32_nd();
 void ls_spmm(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, i64,
              i64, i64, i64, i64, int, int, bool, int, uintptr_t);
@@ -117,6 +119,7 @@ PYBIND11_MODULE(_hip_kernels, m) {
   m.def("spmv_affine", &ls_spmv_affine);
   m.def("affine_const_tiles", &ls_affine_const_tiles);
   m.attr("AFFINE_TILE") = ls_affine_tile();
+  m.def("affine_group", &ls_affine_group);
   m.attr("AFFINE_CONST_F32_ND") = ls_affine_const_f32_nd();
   m.def("spmv_rows", &ls_spmv_rows);
   m.def("spmm", &ls_spmm);

@@ -402,6 +402,23 @@ __global__ __launch_bounds__(LS_THREADS) void spmv_stream_kernel(
 // without either table (in-build A/B).  CONST = false never touches cpat
 // and compiles to what it did without the parameter.
 //
+// Tile groups (narrow stencils with a table, no dot fusion): a -2 tile is
+// 64 rows x 17 B of traffic behind the whole chain kernarg -> D, cpat,
+// table -> x -> store, so one tile per wave leaves the memory system
+// short of requests (profiles/spmv_affine_const.md: 53 % of the copy
+// rate).  Where affine_group(ND, sizeof(T)) > 1 such a launch goes to
+// spmv_affine_groups_kernel instead of spmv_affine_kernel: a wave
+// owns that many consecutive tiles, reads their table entries with one
+// scalar load issued together with D and cpat, and issues the x loads of
+// all its -2 tiles before the first sum; its other tiles then run the
+// per-row body.  The grid counts groups, and the exception rows (the row
+// list of spmv_rows_kernel) run in the first blocks of the same launch.
+// Sums keep their order and shape, so y keeps its bits.
+// LS_SPMV_AFFINE_GROUP=1 launches this kernel and the row list as before,
+// LS_SPMV_AFFINE_FOLD=0 only moves the row list back into its own launch
+// (in-build A/B).  This kernel itself, with and without DOT, is what it
+// was before groups existed (profiles/spmv_affine_groups.md).
+//
 // Same bits as the CONST = false kernel of the same matrix takes one more
 // step in fp32.  The fp64 sum compiles to one fma chain in every
 // instantiation.  The fp32 sum of the CONST = false kernels does not:
@@ -421,6 +438,193 @@ __device__ __forceinline__ T affine_row_sum_unfused(const T (&a)[ND],
 #pragma unroll
   for (int j = 0; j < ND; ++j) acc += a[j] * xv[j];
   return acc;
+}
+
+// Tile groups: a wave of spmv_affine_groups_kernel owns
+// affine_group(ND, sizeof(T)) consecutive tiles.  The x values of all of
+// them take 320 B of registers per lane at the most (eight tiles of the
+// 5-point fp64 stencil: measured against two and four,
+// profiles/spmv_affine_groups.md); a stencil wider than 80 B per row gets
+// no groups and stays on spmv_affine_kernel, which is short of sgprs as
+// it is.
+__host__ __device__ constexpr int affine_group(int nd, int elem_bytes) {
+  if (elem_bytes == 4 && nd > LS_AFFINE_CONST_F32_ND) return 1;  // no table
+  if (nd * elem_bytes > 80) return 1;
+  int g = 1;
+  while (2 * g <= 8 && 2 * g * nd * elem_bytes <= 320) g *= 2;
+  return g;
+}
+
+// The constant-tile kernel of narrow stencils (real dtypes, no dot
+// fusion, affine_group(ND, sizeof(T)) > 1).  tile_base is the value-bound
+// table.  The first rest_blocks blocks do the exception rows rest[0 ..
+// n_rest) (spmv_rows_kernel's loop, same sum order; their y rows have
+// mask == 0 and lie in no full tile, so the groups never touch them), the
+// others do the groups.  Tiles that are not -2 run the per-row body of
+// spmv_affine_kernel, repeated here so that kernel stays as it is.
+template <typename T, int ND>
+__global__ __launch_bounds__(LS_THREADS) void spmv_affine_groups_kernel(
+    const i64* __restrict__ indptr, const T* __restrict__ vals,
+    const T* __restrict__ x, T* __restrict__ y,
+    const int* __restrict__ D, const unsigned char* __restrict__ mask,
+    const i64* __restrict__ tile_base, i64 n_rows, int accumulate,
+    const T* __restrict__ cpat, const i64* __restrict__ rest,
+    const void* __restrict__ indices, i64 n_rest, int rest_blocks,
+    int idx64) {
+  static_assert(!is_cplx<T>::value, "constant tiles: real dtypes only");
+  constexpr bool UNFUSED = sizeof(T) == 4;
+  constexpr int G = affine_group(ND, (int)sizeof(T));
+  static_assert(G > 1, "one tile per wave is spmv_affine_kernel");
+  unsigned blk = blockIdx.x, n_blk = gridDim.x;
+  if (n_rest > 0) {
+    if (blk < (unsigned)rest_blocks) {
+      const i64 i = (i64)blk * LS_THREADS + threadIdx.x;
+      if (i >= n_rest) return;
+      const i64 row = rest[i];
+      const i64 s = indptr[row];
+      const i64 e = indptr[row + 1];
+      T acc = ls_zero<T>();
+      if (idx64) {
+        const i64* ix = static_cast<const i64*>(indices);
+        for (i64 jp = s; jp < e; ++jp) acc += vals[jp] * x[ix[jp]];
+      } else {
+        const int* ix = static_cast<const int*>(indices);
+        for (i64 jp = s; jp < e; ++jp) acc += vals[jp] * x[ix[jp]];
+      }
+      if (accumulate)
+        y[row] += acc;
+      else
+        y[row] = acc;
+      return;
+    }
+    blk -= rest_blocks;
+    n_blk -= rest_blocks;
+  }
+  const int lane = threadIdx.x % WAVE_SIZE;
+  // wave-uniform group index, kept scalar so the table load is scalar.
+  // The launch has LS_THREADS per block: reading blockDim.x here would
+  // put a vector load of the dispatch packet in front of everything.
+  const i64 wave0 = __builtin_amdgcn_readfirstlane(
+      (int)((blk * LS_THREADS + threadIdx.x) / WAVE_SIZE));
+  const i64 n_waves = (i64)n_blk * (LS_THREADS / WAVE_SIZE);
+  const i64 n_tiles = (n_rows + LS_AFFINE_TILE - 1) / LS_AFFINE_TILE;
+  const i64 n_groups = (n_tiles + G - 1) / G;
+  // a group's table entries: contiguous, one scalar load; the last group
+  // may be partial and reads no entry past n_tiles
+  auto load_entries = [&](const i64 t0, i64 (&b)[G])
+                          __attribute__((always_inline)) {
+    if (t0 + G <= n_tiles) {
+#pragma unroll
+      for (int k = 0; k < G; ++k) b[k] = tile_base[t0 + k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < G; ++k)
+        b[k] = t0 + k < n_tiles ? tile_base[t0 + k] : (i64)-1;
+    }
+  };
+  // the first group's entries go out together with D and cpat, the next
+  // group's at the end of each step: the wave's life is a chain of
+  // dependent latencies, and this takes one link out of it
+  i64 b[G];
+  if (wave0 < n_groups) load_entries(wave0 * G, b);
+  int d[ND];
+#pragma unroll
+  for (int j = 0; j < ND; ++j) d[j] = D[j];  // uniform: lands in sgprs
+  T c[ND];
+#pragma unroll
+  for (int j = 0; j < ND; ++j) c[j] = cpat[j];  // uniform, like d
+  // a full tile whose values vary (base >= 0) or a mixed one (base == -1):
+  // spmv_affine_kernel's rows, sum in the same order and shape
+  auto other_tile = [&](const i64 tile, const i64 base)
+                        __attribute__((always_inline)) {
+    const i64 row = tile * LS_AFFINE_TILE + lane;
+    i64 s;
+    if (base >= 0) {
+      s = base + (i64)lane * ND;
+    } else {
+      if (row >= n_rows) return;
+      if (!mask[row]) return;
+      s = indptr[row];
+    }
+    T v[ND], xv[ND];
+#pragma unroll
+    for (int j = 0; j < ND; ++j) v[j] = vals[s + j];
+#pragma unroll
+    for (int j = 0; j < ND; ++j) xv[j] = x[row + d[j]];
+    T acc = ls_zero<T>();
+    if constexpr (UNFUSED) {
+      acc = affine_row_sum_unfused<T, ND>(v, xv);
+    } else {
+#pragma unroll
+      for (int j = 0; j < ND; ++j) acc += v[j] * xv[j];
+    }
+    if (accumulate)
+      y[row] += acc;
+    else
+      y[row] = acc;
+  };
+  // the grid-stride loop advances by groups of G tiles, group-aligned
+  for (i64 grp = wave0; grp < n_groups;) {
+    const i64 t0 = grp * G;
+    unsigned consts = 0;  // the group's -2 tiles (wave-uniform masks)
+    unsigned others = 0;  // its tiles that exist and are not -2
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      if (b[k] == -2)
+        consts |= 1u << k;
+      else if (t0 + k < n_tiles)
+        others |= 1u << k;
+    }
+    if (consts) {
+      // every x load of every -2 tile of the group goes out before the
+      // first sum: G * ND loads in flight per lane, not ND.  Loads and
+      // sums are straight-line code, so each sum waits for its own
+      // tile's loads only; the scalar branches guard the stores.  Slot k
+      // of a group that holds other tiles re-reads the x of the group's
+      // first -2 tile (rows the wave loads anyway, never a row >=
+      // n_rows) and drops the sum.
+      const int k_first = __builtin_ctz(consts);
+      T xv[G][ND];
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        const int ks = ((consts >> k) & 1u) ? k : k_first;
+        const T* xrow = x + ((t0 + ks) * LS_AFFINE_TILE + lane);
+#pragma unroll
+        for (int j = 0; j < ND; ++j) xv[k][j] = xrow[d[j]];
+      }
+      // no sum is scheduled in among the loads
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int k = 0; k < G; ++k) {
+        const i64 row = (t0 + k) * LS_AFFINE_TILE + lane;
+        T acc = ls_zero<T>();
+        if constexpr (UNFUSED) {
+          acc = affine_row_sum_unfused<T, ND>(c, xv[k]);
+        } else {
+#pragma unroll
+          for (int j = 0; j < ND; ++j) acc += c[j] * xv[k][j];
+        }
+        // pins the sum here: without it the compiler sinks a tile's
+        // loads and sum behind the branch, after the other tiles'
+        asm volatile("" : "+v"(acc));
+        if ((consts >> k) & 1u) {
+          if (accumulate)
+            y[row] += acc;
+          else
+            y[row] = acc;
+        }
+      }
+    }
+    // full-varying and mixed tiles of the group, one after another
+    // (rare: 3 % of the tiles on Poisson 4096^2)
+    while (others) {
+      const int k = __builtin_ctz(others);
+      others &= others - 1;
+      other_tile(t0 + k, tile_base[t0 + k]);
+    }
+    grp += n_waves;
+    if (grp < n_groups) load_entries(grp * G, b);
+  }
 }
 
 template <typename T, int ND, bool DOT, bool CONST>
@@ -784,6 +988,8 @@ void spmv_affine_dispatch_nd(const i64* indptr, const T* vals, const T* x,
                              const unsigned char* mask,
                              const i64* tile_base, i64 n_rows, int nd,
                              int accumulate, T* dot_out, const T* cpat,
+                             const i64* rest, i64 n_rest,
+                             const void* indices, int idx64, bool group1,
                              hipStream_t s) {
   // cpat != null: tile_base is the value-bound tile_cbase (-2 tiles)
   if (cpat && (is_cplx<T>::value || !tile_base ||
@@ -791,6 +997,14 @@ void spmv_affine_dispatch_nd(const i64* indptr, const T* vals, const T* x,
     throw std::runtime_error(
         "spmv_affine: constant tiles need a real dtype, a tile table and, "
         "in fp32, nd <= " + std::to_string(LS_AFFINE_CONST_F32_ND));
+  // the constant-tile launch of a narrow stencil takes tile groups, and
+  // the exception rows with them (LS_SPMV_AFFINE_GROUP=1: group1)
+  const bool groups = cpat && !dot_out && !group1 && !is_cplx<T>::value &&
+                      nd >= 1 && nd <= 16 &&
+                      affine_group(nd, (int)sizeof(T)) > 1;
+  if (n_rest > 0 && !groups)
+    throw std::runtime_error(
+        "spmv_affine: a row list rides in a launch with tile groups only");
   // one tile per wave, blocks dispatched in row order: measured 162.6 us
   // uncapped vs 168.6 / 174.6 / 182.9 us at caps 32768 / 16384 / 8192
   // (Poisson 4096^2, profiles/spmv_affine_tiles.md); the grid-stride
@@ -800,13 +1014,33 @@ void spmv_affine_dispatch_nd(const i64* indptr, const T* vals, const T* x,
   int gcap = gcap_env ? atoi(gcap_env) : 0;
   if (gcap < 1) gcap = dot_out ? 8192 : 1 << 22;
   const int grid = grid_1d(n_rows, LS_THREADS, gcap);
+  // groups: the grid counts groups, the row list's blocks come on top
+  const i64 n_tiles = (n_rows + LS_AFFINE_TILE - 1) / LS_AFFINE_TILE;
+  const int rest_blocks =
+      n_rest > 0 ? (int)((n_rest + LS_THREADS - 1) / LS_THREADS) : 0;
   switch (nd) {
+#define LS_AFF_GROUPS(N)                                                   \
+  if constexpr (!is_cplx<T>::value &&                                      \
+                affine_group(N, (int)sizeof(T)) > 1) {                     \
+    if (groups) {                                                          \
+      constexpr int g = affine_group(N, (int)sizeof(T));                   \
+      const int ggrid =                                                    \
+          grid_1d((n_tiles + g - 1) / g, LS_THREADS / WAVE_SIZE, gcap) +   \
+          rest_blocks;                                                     \
+      hipLaunchKernelGGL((spmv_affine_groups_kernel<T, N>), dim3(ggrid),   \
+                         dim3(LS_THREADS), 0, s, indptr, vals, x, y, D,    \
+                         mask, tile_base, n_rows, accumulate, cpat, rest,  \
+                         indices, n_rest, rest_blocks, idx64);             \
+      break;                                                               \
+    }                                                                      \
+  }
 #define LS_AFF_LAUNCH(N, DOT, CONST)                                       \
   hipLaunchKernelGGL((spmv_affine_kernel<T, N, DOT, CONST>), dim3(grid),   \
                      dim3(LS_THREADS), 0, s, indptr, vals, x, y, D, mask,  \
                      tile_base, n_rows, accumulate, dot_out, cpat)
 #define LS_AFF_CASE(N)                                                     \
   case N:                                                                  \
+    LS_AFF_GROUPS(N)                                                       \
     if constexpr (!is_cplx<T>::value) {                                    \
       if (cpat) {                                                          \
         if (dot_out)                                                       \
@@ -827,6 +1061,7 @@ void spmv_affine_dispatch_nd(const i64* indptr, const T* vals, const T* x,
     LS_AFF_CASE(10) LS_AFF_CASE(11) LS_AFF_CASE(12) LS_AFF_CASE(13)
     LS_AFF_CASE(14) LS_AFF_CASE(15) LS_AFF_CASE(16)
 #undef LS_AFF_CASE
+#undef LS_AFF_GROUPS
 #undef LS_AFF_LAUNCH
     default:
       throw std::runtime_error("spmv_affine: nd out of range (1..16)");
@@ -897,12 +1132,17 @@ void ls_spmv_affine(uintptr_t indptr, uintptr_t vals, uintptr_t x,
                     uintptr_t y, uintptr_t D, uintptr_t mask,
                     uintptr_t tile_base, i64 n_rows, int nd, int dtype,
                     bool accumulate, uintptr_t dot_out, uintptr_t cpat,
-                    uintptr_t stream) {
+                    uintptr_t rest, i64 n_rest, uintptr_t indices,
+                    int idx_dtype, int group, uintptr_t stream) {
   // cpat != 0: tile_base is a tile_cbase from ls_affine_const_tiles and
-  // cpat its nd-value pattern (device, the value dtype)
+  // cpat its nd-value pattern (device, the value dtype).  n_rest > 0:
+  // the exception rows rest[0..n_rest) run in the same launch (indices
+  // of idx_dtype, as in ls_spmv_rows).  group == 1: one tile per wave.
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (dot_out && dtype > 1)
     throw std::runtime_error("spmv_affine dot fusion: real dtypes only");
+  if (n_rest > 0 && (idx_dtype < 0 || idx_dtype > 1 || !rest || !indices))
+    throw std::runtime_error("spmv_affine: bad folded row list");
   DISPATCH_VAL_T(dtype, spmv_affine_dispatch_nd<val_t>(
       reinterpret_cast<const i64*>(indptr),
       reinterpret_cast<const val_t*>(vals),
@@ -911,7 +1151,10 @@ void ls_spmv_affine(uintptr_t indptr, uintptr_t vals, uintptr_t x,
       reinterpret_cast<const unsigned char*>(mask),
       reinterpret_cast<const i64*>(tile_base), n_rows, nd,
       accumulate ? 1 : 0, reinterpret_cast<val_t*>(dot_out),
-      reinterpret_cast<const val_t*>(cpat), s));
+      reinterpret_cast<const val_t*>(cpat),
+      reinterpret_cast<const i64*>(rest), n_rest > 0 ? n_rest : 0,
+      reinterpret_cast<const void*>(indices), idx_dtype == 1 ? 1 : 0,
+      group == 1, s));
 }
 
 void ls_affine_const_tiles(uintptr_t vals, uintptr_t tile_base,
@@ -943,6 +1186,12 @@ void ls_affine_const_tiles(uintptr_t vals, uintptr_t tile_base,
 }
 
 int ls_affine_tile() { return LS_AFFINE_TILE; }
+int ls_affine_group(int nd, int dtype) {
+  // tiles per wave of the CONST kernels: dtype 0 = f32, 1 = f64
+  if (nd < 1 || nd > 16 || dtype < 0 || dtype > 1)
+    throw std::runtime_error("affine_group: nd 1..16, real dtypes only");
+  return affine_group(nd, dtype == 0 ? 4 : 8);
+}
 int ls_affine_const_f32_nd() { return LS_AFFINE_CONST_F32_ND; }
 
 void ls_spmv_rows(uintptr_t rows_list, i64 n_list, uintptr_t indptr,
