@@ -1255,6 +1255,11 @@ class csr_array(CompressedBase):
             ones = torch.ones(A._shape[1], dtype=A._data.dtype,
                               device=A._data.device)
             y = out.reshape(-1) if isinstance(out, torch.Tensor) else None
+            if y is not None and y.device != A._data.device:
+                # the kernel writes through a raw pointer: an out on another
+                # device (a host tensor for a GPU matrix) gets a copy
+                y.copy_(ops.spmv(A._indptr, A._indices, A._data, ones))
+                return out
             res = ops.spmv(A._indptr, A._indices, A._data, ones, y)
             return out if out is not None else res
         if axis == 0:

@@ -59,6 +59,44 @@ def spmv(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
     realized as an adjusted base pointer, the same "fake offset dense
     pointer" trick the reference plays on cuSPARSE (spmv.cu:75-90).
 
+    General kernels (GPU, no ``affine``; ``ext.spmv_select`` with the same
+    arguments returns the (kernel, W) a call runs).  ``pair`` selects:
+
+    ====  ==========================================  ==================
+    pair  kernel                                      longest row
+    ====  ==========================================  ==================
+     -1   launcher's choice (below)                   any
+      0   vector, sub-wave of W lanes per row         any
+      1   pair, W lanes x 2 elements per step         any
+      2   stream, 2048 elements per block (PE = 8)    any
+      3   stream, 4096 elements per block (PE = 16)   any
+      4   pair2, a sub-wave serves two rows           any
+      5   sten, one lane per row, 4 pairs             7
+      6   sten, one lane per row, 8 pairs             15
+      7   pairu, 2 lanes per row, 4 pairs each        15
+      8   pairu, 4 lanes per row, 4 pairs each        31
+    ====  ==========================================  ==================
+
+    Codes 1..8 are for real dtypes; complex values run the vector kernel
+    whatever ``pair`` says.  Stream writes boundary rows with atomics into
+    a zeroed y, so with ``accumulate`` codes 2 and 3 run the vector kernel
+    too.  Codes 5..8 read a fixed number of pairs per row and DROP THE
+    ELEMENTS of any longer row without a diagnostic: pass them only for a
+    matrix whose longest row fits.
+
+    ``pair=-1``: W is the largest power of two <= 64 with 4 W <= mean row
+    length; real dtypes take pair (mean >= 3) or vector at that W, unless
+    ``max_nnz >= 0`` says that the longest row has at most 7 / 15 / 31
+    elements, which selects code 5 / 7 / 8.  ``max_nnz`` is trusted, not
+    checked: a value smaller than the true maximum drops elements silently
+    (-1: unknown, never selects 5..8).
+
+    ``w_override`` > 0 replaces W for vector, pair and pair2; a value that
+    is not a power of two <= 64 runs as 64.  ``nt`` (non-temporal loads)
+    and ``swz=1`` (XCD block remap) apply to the vector kernel, ``swz=1``
+    also to pair; ``nt`` wins over ``swz``.  LS_SPMV_GRID caps the grid
+    (default 8192 blocks; read once per process).
+
     ``affine``: stencil plan (csr._affine_plan) — rows with columns ==
     row + D[j] skip the index stream entirely (8 B/nnz instead of
     12 B/nnz), and whole tiles of such rows skip indptr and the mask as

@@ -14,6 +14,8 @@ using i64 = int64_t;
 
 void ls_spmv(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, i64,
              i64, int, int, bool, uintptr_t, int, bool, int, int, i64);
+void ls_spmv_select(i64, i64, int, bool, int, bool, int, int, i64,
+                    const char**, int*);
 void ls_spmv_affine(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
                     uintptr_t, uintptr_t, i64, int, int, bool, uintptr_t,
                     uintptr_t, uintptr_t, i64, uintptr_t, int, int,
@@ -116,6 +118,21 @@ int ls_bicgstab_per_block();
 PYBIND11_MODULE(_hip_kernels, m) {
   m.doc() = "legate_sparse gfx950 HIP kernels";
   m.def("spmv", &ls_spmv);
+  // (kernel, W) that spmv runs for these arguments: "vector", "vector_nt",
+  // "vector_swz", "pair", "pair_swz", "pair2" with the sub-wave width,
+  // "sten" with NP, "pairu" with its W, "stream" with PE
+  m.def("spmv_select",
+        [](i64 n_rows, i64 nnz, int dtype, bool accumulate, int w_override,
+           bool nt, int pair, int swz, i64 max_nnz) {
+          const char* name = nullptr;
+          int W = 0;
+          ls_spmv_select(n_rows, nnz, dtype, accumulate, w_override, nt,
+                         pair, swz, max_nnz, &name, &W);
+          return py::make_tuple(std::string(name), W);
+        },
+        py::arg("n_rows"), py::arg("nnz"), py::arg("dtype"),
+        py::arg("accumulate"), py::arg("w_override"), py::arg("nt"),
+        py::arg("pair"), py::arg("swz"), py::arg("max_nnz"));
   m.def("spmv_affine", &ls_spmv_affine);
   m.def("affine_const_tiles", &ls_affine_const_tiles);
   m.attr("AFFINE_TILE") = ls_affine_tile();

@@ -847,18 +847,36 @@ __global__ __launch_bounds__(LS_THREADS) void spmv_rows_kernel(
   }
 }
 
-template <typename T, typename I>
-void spmv_launch(const i64* indptr, const I* indices, const T* vals,
-                 const T* x, T* y, i64 n_rows, i64 nnz, bool accumulate,
-                 int w_override, bool nt, int pair_mode, int swz_mode,
-                 i64 max_nnz, hipStream_t stream) {
+// Which general kernel a call runs.  The selection lives in one host
+// function so that the launcher and the tests (module.cpp: spmv_select)
+// cannot disagree about it.
+enum SpmvKind {
+  SPMV_VECTOR = 0,  // spmv_vector_kernel<W, NT=false, SWZ=false>
+  SPMV_VECTOR_NT,   // spmv_vector_kernel<W, NT=true,  SWZ=false>
+  SPMV_VECTOR_SWZ,  // spmv_vector_kernel<W, NT=false, SWZ=true>
+  SPMV_PAIR,        // spmv_pair_kernel<W, SWZ=false>
+  SPMV_PAIR_SWZ,    // spmv_pair_kernel<W, SWZ=true>
+  SPMV_PAIR2,       // spmv_pair2_kernel<W, SWZ=false>
+  SPMV_STEN,        // spmv_sten_kernel<NP = W>       (W is 4 or 8)
+  SPMV_PAIRU,       // spmv_pairu_kernel<W, PPL = 4>  (W is 2 or 4)
+  SPMV_STREAM,      // spmv_stream_kernel<PE = W>     (W is 8 or 16)
+};
+struct SpmvChoice {
+  int kind;
+  int W;
+};
+
+SpmvChoice spmv_select(i64 n_rows, i64 nnz, bool is_real, bool accumulate,
+                       int w_override, bool nt, int pair_mode, int swz_mode,
+                       i64 max_nnz) {
   const double mean = n_rows > 0 ? (double)nnz / (double)n_rows : 0.0;
   // W = largest power of two <= mean/2 (measured: ~2 elements per lane,
   // profiles/spmv_sweep_r01.txt)
   int W = 1;
   while (W < 64 && (double)(W * 4) <= mean) W *= 2;
   if (w_override > 0) W = w_override;
-  constexpr bool is_real = !is_cplx<T>::value;
+  // the kernels exist for W = 1, 2, 4, ..., 64: anything else runs as 64
+  if (W < 1 || W > 64 || (W & (W - 1))) W = 64;
   // uniformly short rows: fully unrolled kernels (every load issued
   // before any use) measured 592 vs 525 GF/s on 5-pt Poisson
   // (profiles/spmv_pmc_r01.md)
@@ -873,13 +891,44 @@ void spmv_launch(const i64* indptr, const I* indices, const T* vals,
   const bool pair = (pair_mode < 0) ? (is_real && mean >= 3.0)
                                     : (pair_mode == 1 && is_real);
   const bool swz = swz_mode == 1;
-  // STREAM variant: pair_mode 2 (PE=8) / 3 (PE=16); real dtypes,
-  // non-accumulating only (boundary rows atomicAdd into zeroed y)
+  if (is_real) {
+    // STREAM variant: pair_mode 2 (PE=8) / 3 (PE=16); real dtypes,
+    // non-accumulating only (boundary rows atomicAdd into zeroed y)
+    if ((pair_mode == 2 || pair_mode == 3) && !accumulate && n_rows > 0)
+      return {SPMV_STREAM, pair_mode == 2 ? 8 : 16};
+    if (pair_mode == 7) return {SPMV_PAIRU, 2};
+    if (pair_mode == 8) return {SPMV_PAIRU, 4};
+    if (pair_mode == 5) return {SPMV_STEN, 4};
+    if (pair_mode == 6) return {SPMV_STEN, 8};
+    if (pair_mode == 4) return {SPMV_PAIR2, W};
+    if (pair) return {swz ? SPMV_PAIR_SWZ : SPMV_PAIR, W};
+  }
+  if (nt) return {SPMV_VECTOR_NT, W};
+  if (swz) return {SPMV_VECTOR_SWZ, W};
+  return {SPMV_VECTOR, W};
+}
+
+const char* spmv_kind_name(int kind) {
+  static const char* const names[] = {"vector", "vector_nt", "vector_swz",
+                                      "pair",   "pair_swz",  "pair2",
+                                      "sten",   "pairu",     "stream"};
+  return names[kind];
+}
+
+template <typename T, typename I>
+void spmv_launch(const i64* indptr, const I* indices, const T* vals,
+                 const T* x, T* y, i64 n_rows, i64 nnz, bool accumulate,
+                 int w_override, bool nt, int pair_mode, int swz_mode,
+                 i64 max_nnz, hipStream_t stream) {
+  const SpmvChoice ch =
+      spmv_select(n_rows, nnz, !is_cplx<T>::value, accumulate, w_override,
+                  nt, pair_mode, swz_mode, max_nnz);
   if constexpr (!is_cplx<T>::value) {
-    if ((pair_mode == 2 || pair_mode == 3) && !accumulate && n_rows > 0) {
+    if (ch.kind == SPMV_STREAM) {
       ls_check(hipMemsetAsync(y, 0, n_rows * sizeof(T), stream),
                "spmv memset");
-      if (pair_mode == 2) {
+      if (nnz == 0) return;  // no element block: y = 0 is the product
+      if (ch.W == 8) {
         constexpr int NB = LS_THREADS * 8;
         const i64 grid = (nnz + NB - 1) / NB;
         hipLaunchKernelGGL((spmv_stream_kernel<T, I, 8>), dim3(grid),
@@ -898,76 +947,78 @@ void spmv_launch(const i64* indptr, const I* indices, const T* vals,
   }
   static const char* gcap_env = std::getenv("LS_SPMV_GRID");
   const int gcap = gcap_env ? atoi(gcap_env) : 8192;
+  const int acc = accumulate ? 1 : 0;
+  if constexpr (!is_cplx<T>::value) {
+    if (ch.kind == SPMV_PAIRU) {
+      if (ch.W == 2)
+        hipLaunchKernelGGL((spmv_pairu_kernel<T, I, 2, 4>),
+                           dim3(grid_1d(n_rows, LS_THREADS / 2, gcap)),
+                           dim3(LS_THREADS), 0, stream, indptr, indices,
+                           vals, x, y, n_rows, nnz, acc);
+      else
+        hipLaunchKernelGGL((spmv_pairu_kernel<T, I, 4, 4>),
+                           dim3(grid_1d(n_rows, LS_THREADS / 4, gcap)),
+                           dim3(LS_THREADS), 0, stream, indptr, indices,
+                           vals, x, y, n_rows, nnz, acc);
+      ls_check(hipGetLastError(), "spmv");
+      return;
+    }
+    if (ch.kind == SPMV_STEN) {
+      const int grid3 = grid_1d(n_rows, LS_THREADS, gcap);
+      if (ch.W == 4)
+        hipLaunchKernelGGL((spmv_sten_kernel<T, I, 4>), dim3(grid3),
+                           dim3(LS_THREADS), 0, stream, indptr, indices,
+                           vals, x, y, n_rows, nnz, acc);
+      else
+        hipLaunchKernelGGL((spmv_sten_kernel<T, I, 8>), dim3(grid3),
+                           dim3(LS_THREADS), 0, stream, indptr, indices,
+                           vals, x, y, n_rows, nnz, acc);
+      ls_check(hipGetLastError(), "spmv");
+      return;
+    }
+  }
   auto launch = [&](auto wtag) {
     constexpr int WS = decltype(wtag)::value;
     constexpr int RPB = LS_THREADS / WS;
-    int grid = grid_1d(n_rows, RPB, gcap);
-    if constexpr (!is_cplx<T>::value) {
-      if (pair_mode == 7) {
-        constexpr int RPB7 = LS_THREADS / 2;
-        hipLaunchKernelGGL((spmv_pairu_kernel<T, I, 2, 4>),
-                           dim3(grid_1d(n_rows, RPB7, gcap)),
-                           dim3(LS_THREADS), 0, stream, indptr, indices,
-                           vals, x, y, n_rows, nnz, accumulate ? 1 : 0);
-        return;
-      }
-      if (pair_mode == 8) {
-        constexpr int RPB8 = LS_THREADS / 4;
-        hipLaunchKernelGGL((spmv_pairu_kernel<T, I, 4, 4>),
-                           dim3(grid_1d(n_rows, RPB8, gcap)),
-                           dim3(LS_THREADS), 0, stream, indptr, indices,
-                           vals, x, y, n_rows, nnz, accumulate ? 1 : 0);
-        return;
-      }
-      if (pair_mode == 5 || pair_mode == 6) {
-        int grid3 = grid_1d(n_rows, LS_THREADS, gcap);
-        if (pair_mode == 5)
-          hipLaunchKernelGGL((spmv_sten_kernel<T, I, 4>), dim3(grid3),
+    const int grid = grid_1d(n_rows, RPB, gcap);
+    switch (ch.kind) {
+      case SPMV_PAIR2:
+        if constexpr (!is_cplx<T>::value)
+          hipLaunchKernelGGL((spmv_pair2_kernel<T, I, WS, false>),
+                             dim3(grid_1d(n_rows, RPB * 2, gcap)),
                              dim3(LS_THREADS), 0, stream, indptr, indices,
-                             vals, x, y, n_rows, nnz, accumulate ? 1 : 0);
-        else
-          hipLaunchKernelGGL((spmv_sten_kernel<T, I, 8>), dim3(grid3),
-                             dim3(LS_THREADS), 0, stream, indptr, indices,
-                             vals, x, y, n_rows, nnz, accumulate ? 1 : 0);
-        return;
-      }
-      if (pair_mode == 4) {
-        constexpr int RPB2 = (LS_THREADS / WS) * 2;
-        int grid2 = grid_1d(n_rows, RPB2, gcap);
-        hipLaunchKernelGGL((spmv_pair2_kernel<T, I, WS, false>),
-                           dim3(grid2), dim3(LS_THREADS), 0, stream,
-                           indptr, indices, vals, x, y, n_rows,
-                           nnz, accumulate ? 1 : 0);
-        return;
-      }
-      if (pair) {
-        if (swz)
+                             vals, x, y, n_rows, nnz, acc);
+        break;
+      case SPMV_PAIR_SWZ:
+        if constexpr (!is_cplx<T>::value)
           hipLaunchKernelGGL((spmv_pair_kernel<T, I, WS, true>),
                              dim3(grid), dim3(LS_THREADS), 0, stream,
-                             indptr, indices, vals, x, y, n_rows,
-                             nnz, accumulate ? 1 : 0);
-        else
+                             indptr, indices, vals, x, y, n_rows, nnz, acc);
+        break;
+      case SPMV_PAIR:
+        if constexpr (!is_cplx<T>::value)
           hipLaunchKernelGGL((spmv_pair_kernel<T, I, WS, false>),
                              dim3(grid), dim3(LS_THREADS), 0, stream,
-                             indptr, indices, vals, x, y, n_rows,
-                             nnz, accumulate ? 1 : 0);
-        return;
-      }
+                             indptr, indices, vals, x, y, n_rows, nnz, acc);
+        break;
+      case SPMV_VECTOR_NT:
+        hipLaunchKernelGGL((spmv_vector_kernel<T, I, WS, true, false>),
+                           dim3(grid), dim3(LS_THREADS), 0, stream, indptr,
+                           indices, vals, x, y, n_rows, acc);
+        break;
+      case SPMV_VECTOR_SWZ:
+        hipLaunchKernelGGL((spmv_vector_kernel<T, I, WS, false, true>),
+                           dim3(grid), dim3(LS_THREADS), 0, stream, indptr,
+                           indices, vals, x, y, n_rows, acc);
+        break;
+      default:
+        hipLaunchKernelGGL((spmv_vector_kernel<T, I, WS, false, false>),
+                           dim3(grid), dim3(LS_THREADS), 0, stream, indptr,
+                           indices, vals, x, y, n_rows, acc);
+        break;
     }
-    if (nt)
-      hipLaunchKernelGGL((spmv_vector_kernel<T, I, WS, true, false>),
-                         dim3(grid), dim3(LS_THREADS), 0, stream, indptr,
-                         indices, vals, x, y, n_rows, accumulate ? 1 : 0);
-    else if (swz)
-      hipLaunchKernelGGL((spmv_vector_kernel<T, I, WS, false, true>),
-                         dim3(grid), dim3(LS_THREADS), 0, stream, indptr,
-                         indices, vals, x, y, n_rows, accumulate ? 1 : 0);
-    else
-      hipLaunchKernelGGL((spmv_vector_kernel<T, I, WS, false, false>),
-                         dim3(grid), dim3(LS_THREADS), 0, stream, indptr,
-                         indices, vals, x, y, n_rows, accumulate ? 1 : 0);
   };
-  switch (W) {
+  switch (ch.W) {
     case 1: launch(std::integral_constant<int, 1>{}); break;
     case 2: launch(std::integral_constant<int, 2>{}); break;
     case 4: launch(std::integral_constant<int, 4>{}); break;
@@ -1225,4 +1276,17 @@ void ls_spmv(uintptr_t indptr, uintptr_t indices, uintptr_t vals,
           reinterpret_cast<const val_t*>(x), reinterpret_cast<val_t*>(y),
           n_rows, nnz, accumulate, w_override, nt, pair_mode, swz_mode,
           max_nnz, s))));
+}
+
+// (kernel name, W) that ls_spmv would run for these arguments
+// (module.cpp: spmv_select); no launch
+void ls_spmv_select(i64 n_rows, i64 nnz, int dtype, bool accumulate,
+                    int w_override, bool nt, int pair_mode, int swz_mode,
+                    i64 max_nnz, const char** name, int* W) {
+  if (dtype < 0 || dtype > 3) throw std::runtime_error("bad dtype code");
+  const SpmvChoice ch = spmv_select(n_rows, nnz, dtype <= 1, accumulate,
+                                    w_override, nt, pair_mode, swz_mode,
+                                    max_nnz);
+  *name = spmv_kind_name(ch.kind);
+  *W = ch.W;
 }

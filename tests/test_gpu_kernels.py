@@ -44,7 +44,10 @@ def test_gpu_spmv_dtypes(dtype):
 @pytest.mark.parametrize("nnz_per_row",
                          [1, 3, 5, 7, 9, 11, 15, 17, 31, 33, 101])
 def test_gpu_spmv_row_lengths(nnz_per_row):
-    # sweeps the W (sub-wave width) selection paths of spmv.hip
+    # banded rows: up to 15 per row the affine plan accepts the matrix and
+    # the product runs spmv_affine*; only 17 and 31 (pairu W=4), 33 (pair
+    # W=8) and 101 (pair W=16) reach the general launcher.  Its kernels and
+    # W selection are swept in test_gpu_spmv.py.
     n = 2000
     S = banded_matrix(n, nnz_per_row=min(nnz_per_row, n // 2) | 1)
     x = np.random.default_rng(3).standard_normal(n)
