@@ -60,6 +60,7 @@ HIP_SOURCES = [
     os.path.join(SRC_DIR, "hip", "spgemm.hip"),
     os.path.join(SRC_DIR, "hip", "convert.hip"),
     os.path.join(SRC_DIR, "hip", "solver_ops.hip"),
+    os.path.join(SRC_DIR, "hip", "block_ops.hip"),
     os.path.join(SRC_DIR, "hip", "segsort.hip"),
 ]
 

@@ -25,7 +25,7 @@ from . import comm, ops
 from .base import as_torch_1d
 from .lsarray import lsarray
 from .runtime import runtime
-from .types import to_torch_dtype
+from .types import to_numpy_dtype, to_torch_dtype
 
 
 def _wrap_result(t: torch.Tensor, n_global: int):
@@ -686,3 +686,375 @@ def bicgstab(A, b, x0=None, tol=None, maxiter: Optional[int] = None, M=None,
                 info = st
                 break
     return _wrap_result(x, n), info
+
+
+# ---------------------------------------------------------------------------
+# LOBPCG (docs/DESIGN.md §16): block eigensolver on SpMM + block kernels
+# ---------------------------------------------------------------------------
+def _plain_block(y, device, dt) -> torch.Tensor:
+    """Result of a user or library ``matmat`` -> plain 2-D device tensor."""
+    if not isinstance(y, torch.Tensor):
+        y = torch.from_numpy(np.ascontiguousarray(np.asarray(y)))
+    if type(y) is not torch.Tensor:
+        y = y.as_subclass(torch.Tensor)
+    return y.to(device=device, dtype=dt)
+
+
+def _chol_inv(G: np.ndarray):
+    """Inverse upper Cholesky factor of a Hermitian Gram matrix, after
+    scaling it to unit diagonal: ``G = R^H R`` -> ``R^{-1}``, so that
+    ``V R^{-1}`` is orthonormal.  None when G is not numerically positive
+    definite."""
+    import scipy.linalg as sla
+    G = (G + G.conj().T) / 2
+    d = np.real(np.diag(G))
+    if not np.all(np.isfinite(G)) or np.any(d <= 0):
+        return None
+    s = 1.0 / np.sqrt(d)
+    try:
+        Rf = np.linalg.cholesky(G * s[:, None] * s[None, :]).conj().T
+        Ri = sla.solve_triangular(Rf, np.eye(G.shape[0], dtype=G.dtype))
+    except (np.linalg.LinAlgError, sla.LinAlgError):
+        return None
+    Ri = s[:, None] * Ri
+    return Ri if np.all(np.isfinite(Ri)) else None
+
+
+@track_provenance
+def lobpcg(A, X, B=None, M=None, Y=None, tol=None, maxiter=None,
+           largest=True, verbosityLevel=0, retLambdaHistory=False,
+           retResidualNormsHistory=False, restartControl=20,
+           _block_impl="hip"):
+    """Locally optimal block preconditioned conjugate gradient
+    (scipy.sparse.linalg.lobpcg signature) for the k extremal eigenpairs of
+    a symmetric/Hermitian ``A``.
+
+    ``A`` (a csr_array or LinearOperator) and the optional preconditioner
+    ``M`` are applied only through ``aslinearoperator(.).matmat``; with a
+    csr_array the one operator application per iteration is one SpMM on the
+    active columns.  ``X`` is the (n, k) initial block, global or this
+    rank's (shard, k) rows.  ``B`` and ``Y`` are not implemented.  Unlike
+    scipy there is no dense fallback for small problems: ``n < 3k`` raises.
+
+    All passes over (n, k) blocks run in the block kernels
+    (``ops.block_gram / block_update / block_residual``); the small dense
+    algebra (Cholesky factors, the <= 3k x 3k Rayleigh-Ritz problem) runs
+    on the host in double precision.  That costs three small device-to-host
+    reads per iteration (k norms; the Cholesky Grams; the Gram panels) and
+    the coefficient matrices going back.  Every decision (convergence,
+    active set, restart, breakdown) is taken from all-reduced values, so
+    all ranks branch alike.
+
+    Returns ``(w, V)`` — w a host numpy array of k eigenvalues ordered as
+    scipy orders them (descending for ``largest=True``, ascending
+    otherwise), V this rank's (local_rows, k) block — followed by the
+    eigenvalue and residual-norm histories when requested.  Exhausting
+    ``maxiter`` (default 20) warns and returns the best block seen.
+    """
+    import warnings
+    import scipy.linalg as sla
+
+    if B is not None:
+        raise NotImplementedError("lobpcg: generalized problems (B) are "
+                                  "not implemented")
+    if Y is not None:
+        raise NotImplementedError("lobpcg: constraints (Y) are not "
+                                  "implemented")
+    if _block_impl not in ("hip", "torch"):
+        raise ValueError("_block_impl is 'hip' or 'torch'")
+    Aop = aslinearoperator(A)
+    if Aop.shape[0] != Aop.shape[1]:
+        raise ValueError(f"expected a square operator, got {Aop.shape}")
+    n = Aop.shape[0]
+    device = runtime.device
+    Xin = X if isinstance(X, torch.Tensor) else torch.from_numpy(
+        np.ascontiguousarray(np.asarray(X)))
+    if type(Xin) is not torch.Tensor:
+        Xin = Xin.as_subclass(torch.Tensor)
+    if Xin.ndim != 2:
+        raise ValueError("lobpcg: X must be a 2-D (n, k) block")
+    k = int(Xin.shape[1])
+    if k < 1 or k > ops.BLOCK_KMAX:
+        raise ValueError(f"lobpcg: block size k = {k} is outside "
+                         f"[1, {ops.BLOCK_KMAX}]")
+    if n < 3 * k:
+        raise ValueError(f"lobpcg: n = {n} is below 3k = {3 * k}; use a "
+                         "dense eigensolver for a problem this small")
+    xdt = Xin.dtype if (Xin.dtype.is_floating_point
+                        or Xin.dtype.is_complex) else torch.float64
+    dt = xdt if Aop.dtype is None else torch.promote_types(
+        to_torch_dtype(Aop.dtype), xdt)
+    if dt not in (torch.float32, torch.float64, torch.complex64,
+                  torch.complex128):
+        raise NotImplementedError(f"lobpcg: unsupported dtype {dt}")
+    rdt = ops._real_dtype(dt)
+    hdt = np.complex128 if dt.is_complex else np.float64
+    part = runtime.partition(n)
+    lo, hi = part.lo(runtime.rank), part.hi(runtime.rank)
+    ln = hi - lo
+    if Xin.shape[0] == n and ln != n:
+        Xin = Xin[lo:hi]
+    elif Xin.shape[0] != ln:
+        raise ValueError(f"X row count {Xin.shape[0]} is neither global "
+                         f"({n}) nor the local shard ({ln})")
+    Mop = None if M is None else aslinearoperator(M)
+    if tol is None:
+        tol = float(np.sqrt(np.finfo(to_numpy_dtype(rdt)).eps)) * n
+    tol = float(tol)
+    if maxiter is None:
+        maxiter = 20
+    ws = runtime.world_size
+
+    if _block_impl == "hip":
+        gram_fn, update_fn, resid_fn = (ops.block_gram, ops.block_update,
+                                        ops.block_residual)
+    else:
+        def gram_fn(Xb, Yb, out=None):
+            return ops._block_gram_torch(Xb, Yb, True, out)
+        update_fn = ops._block_update_torch
+        resid_fn = ops._block_residual_torch
+
+    def new_block():
+        return torch.empty((ln, k), dtype=dt, device=device)
+
+    def panel(buf, m):
+        """The first m columns' worth of a (ln, k) buffer as a CONTIGUOUS
+        (ln, m) block (matmat wants contiguous operands)."""
+        return buf if m == k else buf.reshape(-1)[:ln * m].view(ln, m)
+
+    def to_dev(Ch):
+        return torch.from_numpy(np.ascontiguousarray(Ch)).to(
+            device=device, dtype=dt)
+
+    # one flat device buffer takes every small Gram of an iteration, so
+    # they are all-reduced and read with one call each
+    gbuf = torch.empty(12 * k * k, dtype=dt, device=device)
+
+    def grams(pairs):
+        """Host (double) copies of Xb^H Yb for each pair: one all-reduce,
+        one device-to-host read."""
+        off = 0
+        views = []
+        for Xb, Yb in pairs:
+            p, q = int(Xb.shape[1]), int(Yb.shape[1])
+            g = gbuf[off:off + p * q].view(p, q)
+            gram_fn(Xb, Yb, out=g)
+            views.append((off, p, q))
+            off += p * q
+        if ws > 1:
+            comm.allreduce_(gbuf[:off])
+        h = gbuf[:off].cpu().numpy().astype(hdt)
+        return [h[o:o + p * q].reshape(p, q) for o, p, q in views]
+
+    def apply_A(Wb, out):
+        if isinstance(Aop, _SparseMatrixLinearOperator) \
+                and np.dtype(Aop.A.dtype) == to_numpy_dtype(dt):
+            Aop.A.matmat(Wb, out=out)      # SpMM straight into our buffer
+            return out
+        y = _plain_block(Aop.matmat(Wb), device, dt)
+        if tuple(y.shape) != tuple(Wb.shape):
+            raise ValueError(f"A.matmat changed the block shape "
+                             f"{tuple(Wb.shape)} to {tuple(y.shape)}")
+        out.copy_(y)
+        return out
+
+    def pick(lam):
+        order = np.argsort(lam)
+        return order[::-1][:k] if largest else order[:k]
+
+    # ---- buffers: everything (n, k) is allocated here ------------------
+    Xs = [new_block(), new_block(), new_block()]   # current / best / spare
+    AXs = [new_block(), new_block(), new_block()]
+    Rb, Wbuf, AWbuf = new_block(), new_block(), new_block()
+    Pb, APb, Pa_buf, APa_buf = (new_block(), new_block(), new_block(),
+                                new_block())
+    theta = torch.empty(k, dtype=rdt, device=device)
+    nrm = torch.empty(k, dtype=rdt, device=device)
+    cur = 0
+    Xs[0].copy_(Xin.to(device=device, dtype=dt))
+
+    # ---- orthonormalize X, initial Rayleigh-Ritz -----------------------
+    (G,) = grams([(Xs[0], Xs[0])])
+    Ri = _chol_inv(G)
+    if Ri is None:
+        raise ValueError("lobpcg: the initial block X is rank deficient")
+    update_fn(Xs[0], [(Xs[0], to_dev(Ri))], False)
+    apply_A(Xs[0], AXs[0])
+    (H,) = grams([(Xs[0], AXs[0])])
+    lam, Q = np.linalg.eigh((H + H.conj().T) / 2)
+    ii = pick(lam)
+    lam = lam[ii]
+    Qd = to_dev(Q[:, ii])
+    update_fn(Xs[0], [(Xs[0], Qd)], False)
+    update_fn(AXs[0], [(AXs[0], Qd)], False)
+
+    lam_hist = [lam.copy()]
+    res_hist = []
+    active = np.ones(k, dtype=bool)
+    have_P = False
+    best = 0
+    smallest = np.inf
+    it = 0
+    failed = False
+    while True:
+        Xc, AXc = Xs[cur], AXs[cur]
+        theta.copy_(torch.from_numpy(lam.astype(np.float64)))
+        resid_fn(Rb, AXc, Xc, theta, nrm)
+        if ws > 1:
+            comm.allreduce_(nrm)
+        norms = np.sqrt(np.abs(nrm.cpu().numpy().astype(np.float64)))
+        res_hist.append(norms.copy())
+        mean_norm = float(norms.sum()) / k
+        forced = False
+        if mean_norm < smallest:
+            smallest = mean_norm
+            best = cur
+        elif mean_norm > 2.0 ** restartControl * smallest:
+            forced = True
+            apply_A(Xc, AXc)
+        active &= norms > tol
+        na = int(active.sum())
+        if verbosityLevel:
+            print(f"iteration {it}: block size {na}, eigenvalues {lam}, "
+                  f"residual norms {norms}")
+        if na == 0 or it >= maxiter:
+            break
+        act = np.nonzero(active)[0]
+
+        # ---- W = M R[:, active], projected against X, orthonormalized --
+        if na == k:
+            Wa = Rb
+        else:
+            Sel = np.zeros((k, na), dtype=hdt)
+            Sel[act, np.arange(na)] = 1
+            Wa = update_fn(panel(Wbuf, na), [(Rb, to_dev(Sel))], False)
+        if Mop is not None:
+            Wm = _plain_block(Mop.matmat(Wa), device, dt)
+            Wa = panel(Wbuf, na)
+            Wa.copy_(Wm)
+        gxw = gbuf[:k * na].view(k, na)
+        gram_fn(Xc, Wa, out=gxw)
+        if ws > 1:
+            comm.allreduce_(gxw)
+        update_fn(Wa, [(Xc, -gxw)], True)           # no host read
+        restart = forced or not have_P
+        pairs = [(Wa, Wa)] + ([] if restart else [(Pb, Pb)])
+        gs = grams(pairs)
+        Ri = _chol_inv(gs[0])
+        if Ri is None:
+            failed = True
+            break
+        update_fn(Wa, [(Wa, to_dev(Ri))], False)
+        AWa = apply_A(Wa, panel(AWbuf, na))
+        if not restart:
+            Rp = _chol_inv(gs[1][np.ix_(act, act)])
+            if Rp is None:
+                restart = True
+            else:
+                # P[:, active] R^{-1} without a gather: the factor sits in
+                # the active rows of a (k, na) matrix
+                E = np.zeros((k, na), dtype=hdt)
+                E[act, :] = Rp
+                Ed = to_dev(E)
+                Pa = update_fn(panel(Pa_buf, na) if na < k else Pb,
+                               [(Pb, Ed)], False)
+                APa = update_fn(panel(APa_buf, na) if na < k else APb,
+                                [(APb, Ed)], False)
+
+        # ---- Rayleigh-Ritz on [X W P] ----------------------------------
+        C = None
+        while C is None:
+            S = [Xc, Wa] + ([] if restart else [Pa])
+            AS = [AXc, AWa] + ([] if restart else [APa])
+            nb = len(S)
+            idx = [(i, j) for i in range(nb) for j in range(i, nb)]
+            gs = grams([(S[i], AS[j]) for i, j in idx]
+                       + [(S[i], S[j]) for i, j in idx])
+            sizes = [int(b.shape[1]) for b in S]
+            offs = np.concatenate([[0], np.cumsum(sizes)])
+            m = int(offs[-1])
+            gA = np.zeros((m, m), dtype=hdt)
+            gB = np.zeros((m, m), dtype=hdt)
+            for t, (i, j) in enumerate(idx):
+                for gM, blk in ((gA, gs[t]), (gB, gs[len(idx) + t])):
+                    gM[offs[i]:offs[i + 1], offs[j]:offs[j + 1]] = blk
+                    if i != j:
+                        gM[offs[j]:offs[j + 1], offs[i]:offs[i + 1]] = \
+                            blk.conj().T
+            gA = (gA + gA.conj().T) / 2
+            gB = (gB + gB.conj().T) / 2
+            try:
+                if not (np.all(np.isfinite(gA)) and np.all(np.isfinite(gB))):
+                    raise np.linalg.LinAlgError("non-finite Gram matrix")
+                lam_all, vec = sla.eigh(gA, gB, check_finite=False)
+                ii = pick(lam_all)
+                C = vec[:, ii]
+                new_lam = lam_all[ii]
+                if not np.all(np.isfinite(C)):
+                    raise np.linalg.LinAlgError("non-finite Ritz vectors")
+            except (np.linalg.LinAlgError, sla.LinAlgError):
+                C = None
+                if restart:
+                    failed = True
+                    break
+                restart = True       # drop P for this iteration
+        if failed:
+            break
+        lam = new_lam
+        Cx, Cw = to_dev(C[:k]), to_dev(C[k:k + na])
+        # the next X goes to the buffer that is neither current nor best
+        nxt = next(i for i in range(3) if i != cur and i != best)
+        if restart:
+            update_fn(Xs[nxt], [(Xc, Cx), (Wa, Cw)], False)
+            update_fn(AXs[nxt], [(AXc, Cx), (AWa, Cw)], False)
+            update_fn(Pb, [(Wa, Cw)], False)
+            update_fn(APb, [(AWa, Cw)], False)
+        else:
+            Cp = to_dev(C[k + na:])
+            update_fn(Xs[nxt], [(Xc, Cx), (Wa, Cw), (Pa, Cp)], False)
+            update_fn(AXs[nxt], [(AXc, Cx), (AWa, Cw), (APa, Cp)], False)
+            update_fn(Pb, [(Wa, Cw), (Pa, Cp)], False)
+            update_fn(APb, [(AWa, Cw), (APa, Cp)], False)
+        have_P = True
+        cur = nxt
+        it += 1
+        lam_hist.append(lam.copy())
+
+    # ---- post-processing: exact A X and a final Rayleigh-Ritz ----------
+    # (the loop leaves through its convergence test, so the last residual
+    # entry belongs to Xs[cur]; the best block is the one returned)
+    Xf, AXf = Xs[best], AXs[best]
+    apply_A(Xf, AXf)
+    gs = grams([(Xf, AXf), (Xf, Xf)])
+    try:
+        lam, Q = sla.eigh((gs[0] + gs[0].conj().T) / 2,
+                          (gs[1] + gs[1].conj().T) / 2, check_finite=False)
+    except (np.linalg.LinAlgError, sla.LinAlgError) as e:
+        raise ValueError("lobpcg: the final Rayleigh-Ritz failed") from e
+    ii = pick(lam)
+    lam = lam[ii]
+    Qd = to_dev(Q[:, ii])
+    update_fn(Xf, [(Xf, Qd)], False)
+    update_fn(AXf, [(AXf, Qd)], False)
+    theta.copy_(torch.from_numpy(lam.astype(np.float64)))
+    resid_fn(Rb, AXf, Xf, theta, nrm)
+    if ws > 1:
+        comm.allreduce_(nrm)
+    norms = np.sqrt(np.abs(nrm.cpu().numpy().astype(np.float64)))
+    lam_hist.append(lam.copy())
+    res_hist.append(norms.copy())
+    if failed or norms.max() > tol:
+        warnings.warn(
+            f"lobpcg exited at iteration {it} with residual norms {norms} "
+            f"not reaching the requested tolerance {tol}"
+            + (" (the Rayleigh-Ritz problem broke down)" if failed else ""),
+            UserWarning, stacklevel=2)
+    if verbosityLevel:
+        print(f"final eigenvalues {lam}, residual norms {norms}")
+
+    out = [lam.astype(np.float64), lsarray.wrap(Xf, n)]
+    if retLambdaHistory:
+        out.append(lam_hist)
+    if retResidualNormsHistory:
+        out.append(res_hist)
+    return tuple(out)

@@ -1194,3 +1194,218 @@ def bicgstab_xr(x: torch.Tensor, r: torch.Tensor, phat: torch.Tensor,
     out2[0] = (hc * r).sum()
     out2[1] = (rc * r).sum()
     return out2
+
+
+# ---------------------------------------------------------------------------
+# Tall-skinny block algebra for LOBPCG (docs/DESIGN.md §16).  Operands are
+# row-major (n, cols) blocks with unit column stride and any row stride
+# >= cols (a column panel of a wider buffer is fine), 1 <= cols <=
+# BLOCK_KMAX.  Reductions are bit-reproducible: partial slab + fixed-order
+# reduce, no float atomics.
+# ---------------------------------------------------------------------------
+BLOCK_KMAX = 32
+
+def _real_dtype(dt: torch.dtype) -> torch.dtype:
+    return {torch.complex64: torch.float32,
+            torch.complex128: torch.float64}.get(dt, dt)
+
+
+def _block_check(blocks, smalls=()) -> None:
+    """The kernels take raw pointers: dtype, device, shape and strides are
+    checked here.  ``smalls`` are (tensor, shape, dtype) device matrices or
+    vectors that must be contiguous."""
+    ref = blocks[0]
+    if ref.dtype not in _DTYPE_CODE:
+        raise ValueError(f"block ops: unsupported dtype {ref.dtype}")
+    for t in blocks:
+        if t.ndim != 2:
+            raise ValueError("block ops need 2-D blocks")
+        cols = int(t.shape[1])
+        if not 1 <= cols <= BLOCK_KMAX:
+            raise ValueError(
+                f"block ops take 1 to {BLOCK_KMAX} columns, got {cols}")
+        if (t.shape[0] != ref.shape[0] or t.dtype != ref.dtype
+                or t.device != ref.device):
+            raise ValueError("block ops need blocks of one row count, "
+                             "dtype and device")
+        if t.shape[0] > 0 and (t.stride(1) != 1 or t.stride(0) < cols):
+            raise ValueError("block ops need row-major blocks: unit column "
+                             "stride and a row stride >= the column count")
+    for t, shape, dt in smalls:
+        if (tuple(t.shape) != tuple(shape) or t.dtype != dt
+                or t.device != ref.device or not t.is_contiguous()):
+            raise ValueError(
+                f"block ops: need a contiguous {tuple(shape)} {dt} tensor "
+                f"on {ref.device}, got {tuple(t.shape)} {t.dtype} on "
+                f"{t.device}")
+
+
+def _ld(t: torch.Tensor) -> int:
+    # a 0- or 1-row view may report any stride; the kernel never uses it
+    return max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 \
+        else int(t.shape[1])
+
+
+def _block_grid(ext, kind: str, n: int) -> int:
+    """Workgroups the kernel launches for n rows (sizes its slab)."""
+    per = getattr(ext, f"BLOCK_{kind}_PER_BLOCK")
+    cap = getattr(ext, f"BLOCK_{kind}_GRID_CAP")
+    return min(cap, max(1, -(-n // per)))
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> str:
+    """'none', 'same' (identical view) or 'partial' for two blocks."""
+    if a.numel() == 0 or b.numel() == 0 or \
+            a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():
+        return "none"
+    if (a.data_ptr() == b.data_ptr() and a.shape == b.shape
+            and a.stride() == b.stride()):
+        return "same"
+    es = a.element_size()
+
+    def span(t):
+        lo = t.data_ptr()
+        return lo, lo + ((t.shape[0] - 1) * t.stride(0) + t.shape[1]) * es
+    (alo, ahi), (blo, bhi) = span(a), span(b)
+    if ahi <= blo or bhi <= alo:
+        return "none"
+    ld = a.stride(0)
+    if a.shape[0] > 1 and b.shape[0] > 1 and b.stride(0) == ld:
+        # column panels of one wider buffer: disjoint column ranges
+        base = min(alo, blo)
+        ca, cb = (alo - base) // es, (blo - base) // es
+        if max(ca + a.shape[1], cb + b.shape[1]) <= ld and (
+                ca + a.shape[1] <= cb or cb + b.shape[1] <= ca):
+            return "none"
+    return "partial"
+
+
+def block_gram(X: torch.Tensor, Y: torch.Tensor, conj: bool = True,
+               out: torch.Tensor = None) -> torch.Tensor:
+    """``G = X^H Y`` (``X^T Y`` with ``conj=False``): X is (n, p), Y is
+    (n, q), the result a (p, q) device tensor holding this rank's partial
+    sum (the caller all-reduces).  X and Y may alias.  Bit-identical from
+    run to run for the same input."""
+    p, q = int(X.shape[1]), int(Y.shape[1])
+    if out is None:
+        out = torch.empty((p, q), dtype=X.dtype, device=X.device)
+    _block_check((X, Y), [(out, (p, q), X.dtype)])
+    n = int(X.shape[0])
+    if _use_hip(X):
+        ext = _cext.require_hip()
+        slab = torch.empty(_block_grid(ext, "GRAM", n) * p * q, dtype=X.dtype,
+                           device=X.device)
+        ext.block_gram(X.data_ptr(), _ld(X), p, Y.data_ptr(), _ld(Y), q,
+                       out.data_ptr(), slab.data_ptr(), slab.numel(), n,
+                       bool(conj), _code(X), _stream())
+        return out
+    return _block_gram_torch(X, Y, conj, out)
+
+
+_GRAM_TORCH_CHUNK = 1024
+
+
+def _block_gram_torch(X, Y, conj, out):
+    """torch formulation.  A tall block goes through a split-K batched
+    product (chunks of 1024 rows, partial Grams summed): the plain
+    ``X^H @ Y`` puts the whole n-long contraction on one tile — measured
+    450 ms against 0.12 ms for the kernel at n = 4.2M, k = 8, fp64
+    (profiles/lobpcg_r05.md)."""
+    Xt = X.conj() if (conj and X.is_complex()) else X
+    n, c = int(X.shape[0]), _GRAM_TORCH_CHUNK
+    nb = n // c
+    if nb < 64:
+        out.copy_(Xt.transpose(0, 1) @ Y)
+        return out
+    p, q = int(X.shape[1]), int(Y.shape[1])
+    head = torch.bmm(Xt[:nb * c].reshape(nb, c, p).transpose(1, 2),
+                     Y[:nb * c].reshape(nb, c, q)).sum(dim=0)
+    if nb * c < n:
+        head = head + Xt[nb * c:].transpose(0, 1) @ Y[nb * c:]
+    out.copy_(head)
+    return out
+
+
+def block_update(Z: torch.Tensor, terms, accumulate: bool = False
+                 ) -> torch.Tensor:
+    """``Z = sum_i X_i @ C_i (+ Z)`` in one pass.  ``terms`` is a sequence
+    of one to three ``(X_i, C_i)`` pairs: X_i an (n, p_i) block, C_i a
+    contiguous (p_i, q) device matrix, Z an (n, q) block.
+
+    Aliasing: Z may BE one of the X_i (the identical view: same pointer,
+    shape and strides) and may be a column panel of the same wider buffer
+    as an X_i when their column ranges are disjoint.  Any other overlap of
+    Z with an X_i, and any overlap of Z with a C_i, is refused.  The X_i
+    may alias each other freely."""
+    terms = list(terms)
+    if not 1 <= len(terms) <= 3:
+        raise ValueError("block_update takes one to three (X, C) terms")
+    q = int(Z.shape[1])
+    _block_check([Z] + [x for x, _ in terms],
+                 [(c, (int(x.shape[1]), q), Z.dtype) for x, c in terms])
+    for x, c in terms:
+        if _overlap(Z, x) == "partial":
+            raise ValueError("block_update: Z overlaps an input block "
+                             "without being that block")
+        if Z.numel() and c.numel() and Z.untyped_storage().data_ptr() == \
+                c.untyped_storage().data_ptr():
+            raise ValueError("block_update: Z shares storage with a "
+                             "coefficient matrix")
+    n = int(Z.shape[0])
+    if _use_hip(Z):
+        ext = _cext.require_hip()
+        flat = []
+        for i in range(3):
+            x, c = terms[i] if i < len(terms) else terms[0]
+            flat += [x.data_ptr(), _ld(x), int(x.shape[1]), c.data_ptr()]
+        ext.block_update(Z.data_ptr(), _ld(Z), q, len(terms), *flat,
+                         bool(accumulate), n, _code(Z), _stream())
+        return Z
+    return _block_update_torch(Z, terms, accumulate)
+
+
+def _block_update_torch(Z, terms, accumulate):
+    acc = terms[0][0] @ terms[0][1]
+    for x, c in terms[1:]:
+        acc = acc + x @ c
+    if accumulate:
+        acc = acc + Z
+    Z.copy_(acc)
+    return Z
+
+
+def block_residual(R: torch.Tensor, AX: torch.Tensor, X: torch.Tensor,
+                   theta: torch.Tensor, norms: torch.Tensor = None
+                   ) -> torch.Tensor:
+    """``R = AX - X diag(theta)`` and, from the same pass, the k squared
+    column 2-norms of R (this rank's partial sums; the caller all-reduces).
+    ``theta`` and ``norms`` are k-element device vectors of the REAL dtype
+    of the blocks.  R may be AX or X itself; any other overlap is refused.
+    The norms are bit-identical from run to run.  Returns ``norms``."""
+    k = int(X.shape[1])
+    rdt = _real_dtype(X.dtype)
+    if norms is None:
+        norms = torch.empty(k, dtype=rdt, device=X.device)
+    _block_check((R, AX, X), [(theta, (k,), rdt), (norms, (k,), rdt)])
+    if _overlap(R, AX) == "partial" or _overlap(R, X) == "partial":
+        raise ValueError("block_residual: R overlaps an input block "
+                         "without being that block")
+    n = int(X.shape[0])
+    if _use_hip(X):
+        ext = _cext.require_hip()
+        slab = torch.empty(_block_grid(ext, "RESIDUAL", n) * k, dtype=rdt,
+                           device=X.device)
+        ext.block_residual(R.data_ptr(), _ld(R), AX.data_ptr(), _ld(AX),
+                           X.data_ptr(), _ld(X), theta.data_ptr(),
+                           norms.data_ptr(), slab.data_ptr(), slab.numel(),
+                           k, n, _code(X), _stream())
+        return norms
+    return _block_residual_torch(R, AX, X, theta, norms)
+
+
+def _block_residual_torch(R, AX, X, theta, norms):
+    res = AX - X * theta.to(X.dtype).reshape(1, -1)
+    R.copy_(res)
+    norms.copy_((R.real ** 2 + R.imag ** 2).sum(dim=0) if R.is_complex()
+                else (R * R).sum(dim=0))
+    return norms

@@ -114,6 +114,21 @@ void ls_bicgstab_xr(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
                     uintptr_t, uintptr_t, i64, int, uintptr_t);
 int ls_bicgstab_grid_cap();
 int ls_bicgstab_per_block();
+void ls_block_gram(uintptr_t, i64, int, uintptr_t, i64, int, uintptr_t,
+                   uintptr_t, i64, i64, bool, int, uintptr_t);
+void ls_block_update(uintptr_t, i64, int, int, uintptr_t, i64, int,
+                     uintptr_t, uintptr_t, i64, int, uintptr_t, uintptr_t,
+                     i64, int, uintptr_t, bool, i64, int, uintptr_t);
+void ls_block_residual(uintptr_t, i64, uintptr_t, i64, uintptr_t, i64,
+                       uintptr_t, uintptr_t, uintptr_t, i64, int, i64, int,
+                       uintptr_t);
+int ls_block_kmax();
+int ls_block_gram_grid_cap();
+int ls_block_gram_per_block();
+int ls_block_update_grid_cap();
+int ls_block_update_per_block();
+int ls_block_residual_grid_cap();
+int ls_block_residual_per_block();
 
 PYBIND11_MODULE(_hip_kernels, m) {
   m.doc() = "legate_sparse gfx950 HIP kernels";
@@ -179,6 +194,17 @@ PYBIND11_MODULE(_hip_kernels, m) {
     m.attr((std::string(k) + "_GRID_CAP").c_str()) = ls_bicgstab_grid_cap();
     m.attr((std::string(k) + "_PER_BLOCK").c_str()) = ls_bicgstab_per_block();
   }
+  // LOBPCG block kernels (block_ops.hip); PER_BLOCK counts rows
+  m.def("block_gram", &ls_block_gram);
+  m.def("block_update", &ls_block_update);
+  m.def("block_residual", &ls_block_residual);
+  m.attr("BLOCK_KMAX") = ls_block_kmax();
+  m.attr("BLOCK_GRAM_GRID_CAP") = ls_block_gram_grid_cap();
+  m.attr("BLOCK_GRAM_PER_BLOCK") = ls_block_gram_per_block();
+  m.attr("BLOCK_UPDATE_GRID_CAP") = ls_block_update_grid_cap();
+  m.attr("BLOCK_UPDATE_PER_BLOCK") = ls_block_update_per_block();
+  m.attr("BLOCK_RESIDUAL_GRID_CAP") = ls_block_residual_grid_cap();
+  m.attr("BLOCK_RESIDUAL_PER_BLOCK") = ls_block_residual_per_block();
   m.attr("arch") = "gfx950";
   m.attr("spgemm_lds_bins") = py::make_tuple(48, 128, 1024, 4096);
 }
