@@ -1,5 +1,6 @@
 # SPDX-License-Identifier: Apache-2.0
-"""Iterative solvers: CG, GMRES, BiCGSTAB, LinearOperator.
+"""Iterative solvers: CG, GMRES, BiCGSTAB, LOBPCG, LinearOperator; the
+sparse triangular solve and the ILU(0) preconditioner.
 
 Counterpart of the reference's ``legate_sparse/linalg.py`` (linalg.py:85-668).
 The key property preserved is the *async solver pipeline* (SURVEY §3.4):
@@ -1058,3 +1059,325 @@ def lobpcg(A, X, B=None, M=None, Y=None, tol=None, maxiter=None,
     if retResidualNormsHistory:
         out.append(res_hist)
     return tuple(out)
+
+
+# ---------------------------------------------------------------------------
+# Sparse triangular solve and ILU(0) (docs/DESIGN.md §17)
+# ---------------------------------------------------------------------------
+def _plain(t: torch.Tensor) -> torch.Tensor:
+    return t if type(t) is torch.Tensor else t.as_subclass(torch.Tensor)
+
+
+def _tri_analysis(A, lower: bool, unit_diagonal: bool) -> dict:
+    """Per-structure analysis for ``spsolve_triangular``, cached on the
+    matrix by (structure version, lower, unit_diagonal): diagonal
+    positions, the wrong-side and missing-diagonal checks (index
+    arithmetic, one host read) and the level schedule."""
+    key = (A._struct_version, bool(lower), bool(unit_diagonal))
+    cache = getattr(A, "_tri_cache", None)
+    if cache is None or cache.get("version") != A._struct_version:
+        cache = {"version": A._struct_version}
+        A._tri_cache = cache
+    if key not in cache:
+        n = A.shape[0]
+        indptr, indices = A._indptr, A._indices
+        dpos, has = ops.diag_positions(indptr, indices, n)
+        if lower:
+            wrong = indptr[1:] - dpos - has.long()
+        else:
+            wrong = dpos - indptr[:-1]
+        checks = torch.stack([(wrong > 0).any(), (~has).any()]).cpu().tolist()
+        entry = {"dpos": dpos, "wrong_side": bool(checks[0]),
+                 "missing_diag": bool(checks[1]), "sched": None}
+        if not entry["wrong_side"]:
+            entry["sched"] = ops.level_schedule(indptr, indices, n, lower)
+        cache[key] = entry
+    return cache[key]
+
+
+def spsolve_triangular(A, b, lower: bool = True, overwrite_A: bool = False,
+                       overwrite_b: bool = False,
+                       unit_diagonal: bool = False):
+    """Solve ``A x = b`` for a sparse triangular ``A``
+    (scipy.sparse.linalg.spsolve_triangular's signature and semantics).
+
+    ``A`` is a square csr_array (or anything ``csr_array(...)`` accepts),
+    ``b`` is ``(n,)`` or ``(n, k)``, numpy or a torch tensor.  The result
+    has ``b``'s shape and the common dtype.  With ``unit_diagonal`` the
+    stored diagonal entries are ignored.  ``overwrite_b`` solves in place
+    when ``b`` is a row-major tensor of the result's dtype on the runtime
+    device; ``overwrite_A`` is accepted and has no effect (A is never
+    modified).  Any k: the level-scheduled kernels take up to 32 columns a
+    pass and wider blocks go in panels.
+
+    Raises ``ValueError`` for a non-square A, a shape mismatch or stored
+    entries on the wrong side of the diagonal, ``numpy.linalg.LinAlgError``
+    when ``unit_diagonal`` is false and a diagonal entry is missing or
+    zero, and ``NotImplementedError`` at world size above 1.
+    """
+    from .csr import csr_array
+
+    if runtime.world_size > 1:
+        raise NotImplementedError(
+            "spsolve_triangular runs at world size 1 only: a distributed "
+            "triangular solve is a pipeline across ranks (every rank waits "
+            "for the rows of the ranks before it), which is not implemented")
+    if not isinstance(A, csr_array):
+        A = csr_array(A)
+    n = A.shape[0]
+    if A.shape[0] != A.shape[1]:
+        raise ValueError(f"A must be square, got shape {A.shape}")
+    is_t = isinstance(b, torch.Tensor)
+    bt = _plain(b) if is_t else torch.from_numpy(np.asarray(b))
+    if bt.ndim not in (1, 2) or int(bt.shape[0]) != n:
+        raise ValueError(f"b has shape {tuple(bt.shape)}, incompatible with "
+                         f"A of shape {A.shape}")
+    device = A._data.device
+    bdt = bt.dtype if (bt.dtype.is_floating_point or bt.dtype.is_complex) \
+        else torch.float64
+    dt = torch.promote_types(A._data.dtype, bdt)
+    if dt not in (torch.float32, torch.float64, torch.complex64,
+                  torch.complex128):
+        raise NotImplementedError(f"spsolve_triangular: dtype {dt}")
+    info = _tri_analysis(A, lower, unit_diagonal)
+    if info["wrong_side"]:
+        raise ValueError(
+            f"A is not {'lower' if lower else 'upper'} triangular: it stores "
+            f"entries {'above' if lower else 'below'} the diagonal")
+    vals = A._data if A._data.dtype == dt else A._data.to(dt)
+    if not unit_diagonal:
+        if info["missing_diag"] or (n and bool(
+                (vals[info["dpos"]] == 0).any())):
+            raise np.linalg.LinAlgError(
+                "A is singular: a diagonal entry is missing or zero")
+    B2 = bt.reshape(n, 1) if bt.ndim == 1 else bt
+    k = int(B2.shape[1])
+    reuse = (overwrite_b and is_t and bt.dtype == dt and bt.device == device
+             and (bt.ndim == 1 and bt.is_contiguous()
+                  or bt.ndim == 2 and (n <= 1 or k == 0 or (
+                      B2.stride(1) == 1 and B2.stride(0) >= k))))
+    if reuse:
+        X = B2
+    else:
+        X = torch.empty((n, k), dtype=dt, device=device)
+        X.copy_(B2)
+    for c0 in range(0, k, ops.SPTRSV_KMAX):
+        ops.sptrsv(A._indptr, A._indices, vals, info["dpos"], info["sched"],
+                   X[:, c0:c0 + ops.SPTRSV_KMAX], lower=lower,
+                   unit_diagonal=unit_diagonal)
+    out = X.reshape(n) if bt.ndim == 1 else X
+    return _wrap_result(out, n)
+
+
+class ILU0(LinearOperator):
+    """Incomplete LU factorisation on A's own sparsity pattern, as a
+    preconditioner: ``matvec(r)`` applies ``U^-1 L^-1`` with two
+    level-scheduled sweeps over ONE combined factor (strict lower part L
+    with an implied unit diagonal, the rest U).
+
+    ``(L U - A)`` is zero on the pattern of A.  For a symmetric positive
+    definite A with a symmetric pattern the factors satisfy ``U = D L^T``,
+    so the operator ``U^-1 L^-1`` is symmetric (and positive definite where
+    the pivots stay positive): it is a valid ``M`` for ``cg`` and
+    ``lobpcg`` as well as for ``gmres`` and ``bicgstab``.
+
+    At world size W the preconditioner is block-Jacobi: every rank factors
+    the diagonal block of its own rows (entries whose column belongs to
+    another rank are dropped for the factorisation only) and applies it to
+    its own shard with no communication.
+
+    After construction ``matvec`` and ``matmat`` read nothing back from the
+    device and allocate only their output: the sweeps run in place on it.
+    """
+
+    def __init__(self, A, _impl: str = "native"):
+        from .csr import csr_array
+
+        if not isinstance(A, csr_array):
+            A = csr_array(A)
+        if A.shape[0] != A.shape[1]:
+            raise ValueError(f"ilu0 needs a square matrix, got {A.shape}")
+        super().__init__(A.shape, dtype=A.dtype)
+        self._impl = _impl
+        n = A.shape[0]
+        self._lo, self._hi = A._row_lo, A._row_hi
+        ln = self._hi - self._lo
+        indptr, indices = A._indptr, A._indices
+        dev = indptr.device
+        self._src = (indptr, indices)
+        if runtime.world_size > 1:
+            col = indices.long()
+            keep = (col >= self._lo) & (col < self._hi)
+            row_of = torch.repeat_interleave(
+                torch.arange(ln, device=dev), indptr[1:] - indptr[:-1])
+            cnt = torch.bincount(row_of[keep], minlength=ln)
+            indptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev),
+                                torch.cumsum(cnt, 0)])
+            indices = (col[keep] - self._lo).to(indices.dtype).contiguous()
+            self._sel = torch.nonzero(keep).reshape(-1)
+        else:
+            self._sel = None
+        self._indptr, self._indices = indptr, indices
+        dpos, has = ops.diag_positions(indptr, indices, ln)
+        missing = (~has).any().to(torch.int64).reshape(1)
+        if runtime.world_size > 1:
+            comm.allreduce_(missing, op="max")
+        if bool(missing.item()):
+            raise ValueError("ilu0 needs every diagonal entry of A stored")
+        self._dpos = dpos
+        self._sched_l = ops.level_schedule(indptr, indices, ln, True)
+        self._sched_u = ops.level_schedule(indptr, indices, ln, False)
+        self._max_row = int((indptr[1:] - indptr[:-1]).max()) if ln else 0
+        self._flag = torch.empty(1, dtype=torch.int32, device=dev)
+        self._F = None
+        self._factor(A._data)
+
+    # -- factorisation ----------------------------------------------------
+    def _factor(self, data: torch.Tensor) -> None:
+        F = data.clone() if self._sel is None else data[self._sel]
+        ops.ilu0_factor(self._indptr, self._indices, F, self._dpos,
+                        self._sched_l, self._flag, self._max_row,
+                        _impl=self._impl)
+        # the one host read: smallest local row with a bad pivot
+        bad = int(self._flag.item())
+        n = self.shape[0]
+        row = torch.tensor([self._lo + bad if bad < self._hi - self._lo
+                            else n], dtype=torch.int64,
+                           device=runtime.device)
+        if runtime.world_size > 1:
+            comm.allreduce_(row, op="min")
+        row = int(row.item())
+        if row < n:
+            raise RuntimeError(f"ilu0: zero or non-finite pivot in row {row}")
+        self._F = F
+
+    def refactor(self, A2) -> "ILU0":
+        """New values on the SAME sparsity pattern: the level analysis and
+        every index array are reused.  ``ValueError`` for another
+        pattern."""
+        same = (tuple(A2.shape) == self.shape
+                and getattr(A2, "format", None) == "csr"
+                and hasattr(A2, "_indptr"))
+        if same:
+            ip, ix = self._src
+            same = (A2._indptr is ip and A2._indices is ix) or (
+                A2._indptr.shape == ip.shape and A2._indices.shape == ix.shape
+                and torch.equal(A2._indptr, ip)
+                and torch.equal(A2._indices.long(), ix.long()))
+        if runtime.world_size > 1:
+            flag = torch.tensor([0 if same else 1], dtype=torch.int64,
+                                device=runtime.device)
+            comm.allreduce_(flag, op="max")
+            same = not bool(flag.item())
+        if not same:
+            raise ValueError("refactor needs a csr_array with the sparsity "
+                             "pattern of the factored matrix")
+        data = A2._data
+        want = to_torch_dtype(self.dtype)
+        self._factor(data if data.dtype == want else data.to(want))
+        return self
+
+    # -- apply --------------------------------------------------------------
+    @property
+    def levels(self):
+        """(levels of the L sweep, levels of the U sweep)."""
+        return self._sched_l.n_levels, self._sched_u.n_levels
+
+    @property
+    def launches_per_apply(self) -> int:
+        """Kernel launches of one ``matvec`` after chaining."""
+        return self._sched_l.n_launches() + self._sched_u.n_launches()
+
+    def _sweeps(self, X: torch.Tensor) -> None:
+        for sched, lower in ((self._sched_l, True), (self._sched_u, False)):
+            ops.sptrsv(self._indptr, self._indices, self._F, self._dpos,
+                       sched, X, lower=lower, unit_diagonal=lower,
+                       _impl=self._impl)
+
+    def matvec(self, r, out=None):
+        x = _to_local_vec(r, self.shape[0], self.dtype, self._F.device)
+        if out is None:
+            out = torch.empty_like(x)
+        else:
+            out = _plain(out)
+            if out.shape != x.shape or out.dtype != x.dtype \
+                    or not out.is_contiguous():
+                raise ValueError("ilu0.matvec: out must be a contiguous "
+                                 "vector of the operator's dtype")
+        if out.data_ptr() != x.data_ptr():
+            out.copy_(x)
+        self._sweeps(out.view(-1, 1))
+        return out
+
+    def solve(self, r):
+        """``U^-1 L^-1 r`` (scipy's ``spilu(...).solve``)."""
+        return _wrap_result(self.matvec(r), self.shape[0])
+
+    def matmat(self, R):
+        """``U^-1 L^-1 R`` for an (n, k) block, the factor streamed once
+        per panel of at most 32 columns."""
+        if getattr(R, "ndim", None) != 2:
+            raise ValueError("expected a 2-D block of column vectors")
+        Rt = _plain(R) if isinstance(R, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(np.asarray(R)))
+        n, ln = self.shape[0], self._hi - self._lo
+        if Rt.shape[0] == n and ln != n:
+            Rt = Rt[self._lo:self._hi]
+        elif Rt.shape[0] != ln:
+            raise ValueError(f"block row count {Rt.shape[0]} is neither "
+                             f"global ({n}) nor the local shard ({ln})")
+        k = int(Rt.shape[1])
+        out = torch.empty((ln, k), dtype=self._F.dtype, device=self._F.device)
+        out.copy_(Rt)
+        for c0 in range(0, k, ops.SPTRSV_KMAX):
+            self._sweeps(out[:, c0:c0 + ops.SPTRSV_KMAX])
+        return out
+
+    def rmatvec(self, x, out=None):
+        raise NotImplementedError("ilu0: rmatvec is not implemented")
+
+    def rmatmat(self, X):
+        raise NotImplementedError("ilu0: rmatmat is not implemented")
+
+    # -- inspection ---------------------------------------------------------
+    def factor_local(self):
+        """This rank's combined factor as ``(indptr, indices, values)`` of
+        its diagonal block (local column numbers)."""
+        return self._indptr, self._indices, self._F
+
+    def _split(self):
+        import scipy.sparse as sp
+        from .csr import csr_array
+
+        if runtime.world_size > 1:
+            raise NotImplementedError(
+                "L and U are per-rank diagonal blocks at world size above "
+                "1; read them with factor_local()")
+        S = sp.csr_matrix((self._F.cpu().numpy(), self._indices.cpu().numpy(),
+                           self._indptr.cpu().numpy()), shape=self.shape)
+        L = sp.tril(S, -1, format="csr") + sp.identity(
+            self.shape[0], dtype=S.dtype, format="csr")
+        return csr_array(L.tocsr()), csr_array(sp.triu(S, 0, format="csr"))
+
+    @property
+    def L(self):
+        """Unit lower factor with its ones stored (built on the host: for
+        inspection and tests, not on the apply path)."""
+        return self._split()[0]
+
+    @property
+    def U(self):
+        """Upper factor with its diagonal."""
+        return self._split()[1]
+
+
+def ilu0(A) -> ILU0:
+    """ILU(0) of a square csr_array whose every diagonal entry is stored,
+    as a ``LinearOperator`` any solver here takes as ``M=``::
+
+        M = linalg.ilu0(A); x, info = linalg.bicgstab(A, b, M=M)
+
+    ``ValueError`` for a missing diagonal entry (before any kernel runs),
+    ``RuntimeError`` naming the global row for a zero or non-finite pivot.
+    See :class:`ILU0`."""
+    return ILU0(A)

@@ -1409,3 +1409,322 @@ def _block_residual_torch(R, AX, X, theta, norms):
     norms.copy_((R.real ** 2 + R.imag ** 2).sum(dim=0) if R.is_complex()
                 else (R * R).sum(dim=0))
     return norms
+
+
+# ---------------------------------------------------------------------------
+# Level-scheduled sparse triangular solve and ILU(0) (docs/DESIGN.md §17).
+# The matrix is a LOCAL square CSR (columns are local row numbers, sorted
+# within a row).  Rows are grouped into dependency levels on the host once
+# per structure; the levels become a launch plan of "wide" launches (one
+# level, many workgroups) and "chain" launches (a run of narrow levels, one
+# workgroup, a barrier between levels).  No kernel waits on another
+# workgroup.
+# ---------------------------------------------------------------------------
+SPTRSV_KMAX = 32
+# a level with at most this many rows joins a chain (the extension exports
+# the same numbers; tests compare them)
+SPTRSV_CHAIN_ROWS = 256
+SPTRSV_GRID_CAP = 4096
+_I32_MAX = 2 ** 31 - 1
+_SPTRSV_IMPLS = ("native", "torch")
+
+
+def diag_positions(indptr: torch.Tensor, indices: torch.Tensor, n: int,
+                   row_offset: int = 0):
+    """``(diag_pos, has_diag)``: the position of the diagonal in every row
+    of a CSR with sorted rows, or the insertion point where it is not
+    stored, and a mask of the rows that store it.  Index arithmetic on the
+    matrix's device."""
+    dev = indptr.device
+    rows = torch.arange(n, device=dev)
+    row_of = torch.repeat_interleave(rows, indptr[1:] - indptr[:-1])
+    col = indices.long() - int(row_offset)
+    cnt = torch.bincount(row_of[col < row_of], minlength=n)
+    dpos = (indptr[:-1] + cnt).contiguous()
+    if col.numel():
+        at = col[dpos.clamp(max=col.numel() - 1)]
+        has = (dpos < indptr[1:]) & (at == rows)
+    else:
+        has = torch.zeros(n, dtype=torch.bool, device=dev)
+    return dpos, has
+
+
+def sptrsv_plan(level_ptr, chain_rows: int):
+    """Launch plan for the levels ``level_ptr`` describes: an (m, 3) int64
+    numpy array of ``(kind, lv_lo, lv_hi)``, kind 0 = wide (one level with
+    more than ``chain_rows`` rows), 1 = chain (a maximal run of levels of
+    at most ``chain_rows`` rows each)."""
+    import numpy as np
+    w = np.diff(np.asarray(level_ptr, dtype=np.int64))
+    if w.size == 0:
+        return np.zeros((0, 3), dtype=np.int64)
+    narrow = w <= int(chain_rows)
+    prev_narrow = np.concatenate([[False], narrow[:-1]])
+    lo = np.flatnonzero(~narrow | ~prev_narrow)
+    hi = np.concatenate([lo[1:], [w.size]])
+    return np.ascontiguousarray(
+        np.stack([narrow[lo].astype(np.int64), lo, hi], axis=1))
+
+
+class LevelSchedule:
+    """Rows sorted by dependency level (``order``, stable within a level)
+    and the level boundaries (``level_ptr``), on the host and on the
+    matrix's device, with the launch plans built from them."""
+
+    def __init__(self, order: torch.Tensor, level_ptr: torch.Tensor, device,
+                 lower: bool):
+        self.lower = bool(lower)
+        self.order_host = order
+        self.level_ptr_host = level_ptr.contiguous()
+        self.n_levels = int(level_ptr.numel()) - 1
+        self.order = order.to(device)
+        self.level_ptr = self.level_ptr_host.to(device)
+        self._plans = {}
+        self._torch_levels = None
+
+    def plan(self, chain_rows=None) -> torch.Tensor:
+        c = SPTRSV_CHAIN_ROWS if chain_rows is None else int(chain_rows)
+        if c < 1:
+            raise ValueError("_chain_rows must be at least 1")
+        if c not in self._plans:
+            self._plans[c] = torch.from_numpy(
+                sptrsv_plan(self.level_ptr_host.numpy(), c))
+        return self._plans[c]
+
+    def n_launches(self, chain_rows=None) -> int:
+        return int(self.plan(chain_rows).shape[0])
+
+    def torch_levels(self, indptr, indices, dpos):
+        """Per-level index tensors of the ``_impl="torch"`` arm:
+        ``(rows, entries, columns, segment ids, diagonal positions)``."""
+        if self._torch_levels is not None:
+            return self._torch_levels
+        dev = indptr.device
+        rows = self.order
+        n = int(rows.numel())
+        if self.lower:
+            s, e = indptr[rows], dpos[rows]
+        else:
+            nnz = int(indices.numel())
+            e = indptr[rows + 1]
+            d = dpos[rows]
+            if nnz:
+                has = (d < e) & (indices[d.clamp(max=nnz - 1)].long() == rows)
+            else:
+                has = torch.zeros(n, dtype=torch.bool, device=dev)
+            s = d + has.long()
+        cnt = e - s
+        off = torch.cumsum(cnt, 0) - cnt
+        seg = torch.repeat_interleave(torch.arange(n, device=dev), cnt)
+        ent = s[seg] + (torch.arange(seg.numel(), device=dev) - off[seg])
+        cols = indices[ent].long()
+        ends = torch.cat([off, cnt.sum().reshape(1)])
+        lp = self.level_ptr_host.tolist()
+        eb = ends[self.level_ptr].cpu().tolist()
+        out = []
+        for lv in range(self.n_levels):
+            a, b = lp[lv], lp[lv + 1]
+            out.append((rows[a:b], ent[eb[lv]:eb[lv + 1]],
+                        cols[eb[lv]:eb[lv + 1]],
+                        seg[eb[lv]:eb[lv + 1]] - a, dpos[rows[a:b]]))
+        self._torch_levels = out
+        return out
+
+
+def level_schedule(indptr: torch.Tensor, indices: torch.Tensor, n: int,
+                   lower: bool, row_offset: int = 0) -> LevelSchedule:
+    """Level analysis of the lower or upper triangle: one sequential
+    O(nnz) pass on the host (``indptr`` / ``indices`` of a GPU matrix are
+    copied there once).  Entries whose column falls outside
+    ``[row_offset, row_offset + n)`` are not dependencies."""
+    cpu = _cext.require_cpu()
+    ip = indptr.to("cpu", torch.int64).contiguous()
+    ix = indices.to("cpu").contiguous()
+    order = torch.empty(n, dtype=torch.int64)
+    lptr = torch.zeros(n + 1, dtype=torch.int64)
+    nl = cpu.level_schedule(ip.data_ptr(), ix.data_ptr(), int(n), bool(lower),
+                            int(row_offset), order.data_ptr(),
+                            lptr.data_ptr(), _icode(ix)) if n else 0
+    return LevelSchedule(order, lptr[:nl + 1].clone(), indptr.device, lower)
+
+
+def _tri_check(indptr, indices, vals, diag_pos, sched, what):
+    n = int(indptr.numel()) - 1
+    if vals.dtype not in _DTYPE_CODE or indices.dtype not in _IDX_CODE:
+        raise ValueError(f"{what}: unsupported value or index dtype")
+    for t, dt, ne in ((indptr, torch.int64, n + 1),
+                      (diag_pos, torch.int64, n),
+                      (sched.order, torch.int64, n),
+                      (indices, indices.dtype, vals.numel()),
+                      (vals, vals.dtype, vals.numel())):
+        if (t.dtype != dt or t.numel() != ne or t.device != vals.device
+                or not t.is_contiguous()):
+            raise ValueError(f"{what}: needs contiguous CSR arrays, diag_pos "
+                             f"and schedule of one matrix on one device")
+    return n
+
+
+def _cap_arg(grid_cap) -> int:
+    if grid_cap is None:
+        return 0
+    if not 1 <= int(grid_cap) <= SPTRSV_GRID_CAP:
+        raise ValueError(f"_grid_cap outside [1, {SPTRSV_GRID_CAP}]")
+    return int(grid_cap)
+
+
+def sptrsv(indptr: torch.Tensor, indices: torch.Tensor, vals: torch.Tensor,
+           diag_pos: torch.Tensor, sched: LevelSchedule, X: torch.Tensor,
+           lower: bool = True, unit_diagonal: bool = False,
+           _impl: str = "native", _grid_cap=None, _chain_rows=None
+           ) -> torch.Tensor:
+    """Solve ``T X = X`` IN PLACE, T the lower (upper) triangle of the
+    square local CSR: row i uses the entries ``[indptr[i], diag_pos[i])``
+    (``(diag_pos[i], indptr[i+1])``) and divides by the stored diagonal
+    unless ``unit_diagonal``.  X is an (n, k) row-major block, 1 <= k <=
+    SPTRSV_KMAX, with unit column stride and any row stride >= k.
+    ``sched`` is ``level_schedule(...)`` of the same triangle.  Without
+    ``unit_diagonal`` every row must store its diagonal (the caller checks:
+    ``diag_positions`` returns the mask).  Bit-identical from run to run.  ``_grid_cap`` / ``_chain_rows`` override the launch
+    shape for tests."""
+    if _impl not in _SPTRSV_IMPLS:
+        raise ValueError(f"_impl must be one of {_SPTRSV_IMPLS}")
+    n = _tri_check(indptr, indices, vals, diag_pos, sched, "sptrsv")
+    if sched.lower != bool(lower):
+        raise ValueError("sptrsv: the schedule is of the other triangle")
+    if X.ndim != 2 or int(X.shape[0]) != n:
+        raise ValueError(f"sptrsv needs an ({n}, k) block")
+    k = int(X.shape[1])
+    if not 1 <= k <= SPTRSV_KMAX:
+        raise ValueError(f"sptrsv takes 1 to {SPTRSV_KMAX} columns, got {k}")
+    if X.dtype != vals.dtype or X.device != vals.device:
+        raise ValueError("sptrsv: X must have the matrix's dtype and device")
+    if n > 1 and (X.stride(1) != 1 or X.stride(0) < k):
+        raise ValueError("sptrsv needs a row-major block: unit column "
+                         "stride and a row stride >= the column count")
+    if n == 1 and k > 1 and X.stride(1) != 1:
+        raise ValueError("sptrsv needs unit column stride")
+    cap = _cap_arg(_grid_cap)
+    plan = sched.plan(_chain_rows)
+    if n == 0:
+        return X
+    if _impl == "torch" or (X.is_cuda and settings.force_cpu_fallback):
+        return _sptrsv_torch(indptr, indices, vals, diag_pos, sched, X,
+                             unit_diagonal)
+    if X.is_cuda:
+        ext = _cext.require_hip()
+        ext.sptrsv(indptr.data_ptr(), indices.data_ptr(), vals.data_ptr(),
+                   diag_pos.data_ptr(), sched.order.data_ptr(),
+                   sched.level_ptr.data_ptr(), X.data_ptr(), _ld(X), k, n,
+                   vals.numel(), sched.level_ptr_host.data_ptr(),
+                   sched.n_levels, plan.data_ptr(), int(plan.shape[0]),
+                   bool(lower), bool(unit_diagonal), cap, _code(vals),
+                   _icode(indices), _stream())
+        return X
+    _cext.require_cpu().sptrsv(
+        indptr.data_ptr(), indices.data_ptr(), vals.data_ptr(),
+        diag_pos.data_ptr(), X.data_ptr(), _ld(X), k, n, bool(lower),
+        bool(unit_diagonal), _code(vals), _icode(indices))
+    return X
+
+
+def _sptrsv_torch(indptr, indices, vals, dpos, sched, X, unit):
+    """Per-level index ops in torch (debug arm and the A/B benchmark)."""
+    for rows, ent, cols, seg, drows in sched.torch_levels(indptr, indices,
+                                                          dpos):
+        xi = X[rows]
+        if ent.numel():
+            xi = xi.index_add(0, seg, vals[ent].unsqueeze(1) * X[cols],
+                              alpha=-1)
+        if not unit:
+            xi = xi / vals[drows].unsqueeze(1)
+        X[rows] = xi
+    return X
+
+
+def ilu0_factor(indptr: torch.Tensor, indices: torch.Tensor, F: torch.Tensor,
+                diag_pos: torch.Tensor, sched: LevelSchedule,
+                flag: torch.Tensor, max_row_nnz: int,
+                _impl: str = "native", _grid_cap=None, _chain_rows=None
+                ) -> torch.Tensor:
+    """IKJ ILU(0) IN PLACE on ``F`` (the values of a square local CSR whose
+    every diagonal entry is stored, ``diag_pos`` pointing at them): on
+    return the strict lower part holds L (unit diagonal implied) and the
+    rest U.  ``sched`` is the LOWER schedule.  ``flag`` (one int32 on the
+    matrix's device) receives the smallest row whose pivot is zero or not
+    finite, or 2**31 - 1; nothing is read back here.  ``max_row_nnz`` is
+    the longest row (picks the sub-wave width)."""
+    if _impl not in _SPTRSV_IMPLS:
+        raise ValueError(f"_impl must be one of {_SPTRSV_IMPLS}")
+    n = _tri_check(indptr, indices, F, diag_pos, sched, "ilu0_factor")
+    if not sched.lower:
+        raise ValueError("ilu0_factor needs the lower schedule")
+    if (flag.dtype != torch.int32 or flag.numel() != 1
+            or flag.device != F.device):
+        raise ValueError("ilu0_factor: flag is one int32 on the matrix's "
+                         "device")
+    if n > _I32_MAX:
+        raise ValueError("ilu0_factor: too many local rows")
+    cap = _cap_arg(_grid_cap)
+    plan = sched.plan(_chain_rows)
+    flag.fill_(_I32_MAX)
+    if n == 0:
+        return F
+    if _impl == "torch" or (F.is_cuda and settings.force_cpu_fallback):
+        return _ilu0_factor_torch(indptr, indices, F, diag_pos, sched, flag)
+    if F.is_cuda:
+        ext = _cext.require_hip()
+        ext.ilu0_factor(indptr.data_ptr(), indices.data_ptr(), F.data_ptr(),
+                        diag_pos.data_ptr(), sched.order.data_ptr(),
+                        sched.level_ptr.data_ptr(), flag.data_ptr(), n,
+                        F.numel(), sched.level_ptr_host.data_ptr(),
+                        sched.n_levels, plan.data_ptr(), int(plan.shape[0]),
+                        int(max_row_nnz) > 32, cap, _code(F),
+                        _icode(indices), _stream())
+        return F
+    bad = _cext.require_cpu().ilu0_factor(
+        indptr.data_ptr(), indices.data_ptr(), F.data_ptr(),
+        diag_pos.data_ptr(), n, _code(F), _icode(indices))
+    if bad < n:
+        flag.fill_(int(bad))
+    return F
+
+
+def _ilu0_factor_torch(indptr, indices, F, dpos, sched, flag):
+    """Per-level torch formulation: within a level, step p handles the p-th
+    lower entry of every row that has one; the (row, column) targets of the
+    updates are found by searchsorted in the row-major keys."""
+    dev = F.device
+    n = int(indptr.numel()) - 1
+    nnz = int(F.numel())
+    row_of = torch.repeat_interleave(torch.arange(n, device=dev),
+                                     indptr[1:] - indptr[:-1])
+    idx = indices.long()
+    keys = row_of * n + idx
+    nlow = dpos - indptr[:-1]
+    lp = sched.level_ptr_host.tolist()
+    for lv in range(1, sched.n_levels):
+        rows = sched.order[lp[lv]:lp[lv + 1]]
+        low = nlow[rows]
+        for p in range(int(low.max())):
+            act = rows[low > p]
+            pos = indptr[act] + p
+            kr = idx[pos]
+            aik = F[pos] / F[dpos[kr]]
+            F[pos] = aik
+            us = dpos[kr] + 1
+            cnt = indptr[kr + 1] - us
+            off = torch.cumsum(cnt, 0) - cnt
+            seg = torch.repeat_interleave(
+                torch.arange(act.numel(), device=dev), cnt)
+            q = us[seg] + (torch.arange(seg.numel(), device=dev) - off[seg])
+            tgt = act[seg] * n + idx[q]
+            loc = torch.searchsorted(keys, tgt).clamp(max=nnz - 1)
+            hit = keys[loc] == tgt
+            loc, seg, q = loc[hit], seg[hit], q[hit]
+            F[loc] = F[loc] - aik[seg] * F[q]      # distinct positions
+    piv = F[dpos]
+    bad = (piv == 0) | ~torch.isfinite(piv)
+    first = torch.where(bad, torch.arange(n, device=dev),
+                        torch.full((), _I32_MAX, device=dev)).min()
+    flag.copy_(first.to(torch.int32).reshape(1))
+    return F

@@ -15,7 +15,9 @@
 
 #include <pybind11/pybind11.h>
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <limits>
 #include <complex>
 #include <vector>
 #include <stdexcept>
@@ -200,7 +202,140 @@ static void spgemm_numeric(uintptr_t A_indptr, uintptr_t A_indices,
           reinterpret_cast<scalar_t*>(C_vals)))));
 }
 
+// ---------------------------------------------------------------------------
+// Level-scheduled triangular solve / ILU(0) (docs/DESIGN.md §17)
+// ---------------------------------------------------------------------------
+// One sequential O(nnz) pass: level[i] = 1 + max(level[j]) over the
+// off-diagonal entries of row i on the solve's side (columns below i for
+// lower, above i for upper), 0 when there are none.  Columns are global:
+// local column = indices - row_offset, and entries outside [0, n) are not
+// dependencies.  The upper sweep walks the rows from the bottom.  Writes
+// `order` (n rows sorted by level, ascending row number within a level) and
+// `level_ptr` (room for n + 1 entries); returns the number of levels.
+template <typename I>
+static i64 level_schedule_impl(const i64* indptr, const I* indices, i64 n,
+                               bool lower, i64 row_offset, i64* order,
+                               i64* level_ptr) {
+  std::vector<i64> level(n, 0);
+  i64 n_levels = 0;
+  for (i64 t = 0; t < n; ++t) {
+    const i64 i = lower ? t : n - 1 - t;
+    i64 lv = 0;
+    for (i64 jp = indptr[i]; jp < indptr[i + 1]; ++jp) {
+      const i64 j = (i64)indices[jp] - row_offset;
+      if (j < 0 || j >= n) continue;
+      if (lower ? j < i : j > i) lv = std::max(lv, level[j] + 1);
+    }
+    level[i] = lv;
+    n_levels = std::max(n_levels, lv + 1);
+  }
+  std::fill(level_ptr, level_ptr + n_levels + 1, i64(0));
+  for (i64 i = 0; i < n; ++i) ++level_ptr[level[i] + 1];
+  for (i64 l = 0; l < n_levels; ++l) level_ptr[l + 1] += level_ptr[l];
+  std::vector<i64> fill(level_ptr, level_ptr + n_levels);
+  for (i64 i = 0; i < n; ++i) order[fill[level[i]]++] = i;
+  return n_levels;
+}
+
+static i64 level_schedule(uintptr_t indptr, uintptr_t indices, i64 n,
+                          bool lower, i64 row_offset, uintptr_t order,
+                          uintptr_t level_ptr, int idx_dtype) {
+  i64 r = 0;
+  DISPATCH_IDX(idx_dtype, (r = level_schedule_impl<index_t>(
+      reinterpret_cast<const i64*>(indptr),
+      reinterpret_cast<const index_t*>(indices), n, lower, row_offset,
+      reinterpret_cast<i64*>(order), reinterpret_cast<i64*>(level_ptr))));
+  return r;
+}
+
+// In-place sweep X <- T^{-1} X over a square local CSR; X is (n, k) with
+// row stride ld.  dpos[i] is the diagonal's position in row i or its
+// insertion point.
+template <typename T, typename I>
+static void sptrsv_impl(const i64* indptr, const I* indices, const T* vals,
+                        const i64* dpos, T* x, i64 ld, i64 k, i64 n,
+                        bool lower, bool unit) {
+  for (i64 t = 0; t < n; ++t) {
+    const i64 i = lower ? t : n - 1 - t;
+    const i64 d = dpos[i];
+    i64 s, e;
+    if (lower) {
+      s = indptr[i];
+      e = d;
+    } else {
+      e = indptr[i + 1];
+      s = (d < e && (i64)indices[d] == i) ? d + 1 : d;
+    }
+    T* xi = x + i * ld;
+    for (i64 jp = s; jp < e; ++jp) {
+      const T v = vals[jp];
+      const T* xr = x + (i64)indices[jp] * ld;
+      for (i64 q = 0; q < k; ++q) xi[q] -= v * xr[q];
+    }
+    if (!unit) {
+      const T dv = vals[d];
+      for (i64 q = 0; q < k; ++q) xi[q] /= dv;
+    }
+  }
+}
+
+static void sptrsv(uintptr_t indptr, uintptr_t indices, uintptr_t vals,
+                   uintptr_t dpos, uintptr_t x, i64 ld, i64 k, i64 n,
+                   bool lower, bool unit, int dtype, int idx_dtype) {
+  DISPATCH_VAL(dtype, DISPATCH_IDX(idx_dtype, (sptrsv_impl<scalar_t, index_t>(
+      reinterpret_cast<const i64*>(indptr),
+      reinterpret_cast<const index_t*>(indices),
+      reinterpret_cast<const scalar_t*>(vals),
+      reinterpret_cast<const i64*>(dpos), reinterpret_cast<scalar_t*>(x), ld,
+      k, n, lower, unit))));
+}
+
+template <typename T>
+static bool bad_pivot(const T& v) {
+  return v == T(0) || !(std::abs(v) <= std::numeric_limits<double>::max());
+}
+
+// IKJ ILU(0) in place on f (A's values on entry); every diagonal is stored.
+// Returns the first row whose pivot is zero or not finite, or n.
+template <typename T, typename I>
+static i64 ilu0_factor_impl(const i64* indptr, const I* indices, T* f,
+                            const i64* dpos, i64 n) {
+  i64 bad = n;
+  for (i64 i = 0; i < n; ++i) {
+    const i64 e = indptr[i + 1], d = dpos[i];
+    for (i64 p = indptr[i]; p < d; ++p) {
+      const i64 kr = (i64)indices[p];
+      const T aik = f[p] / f[dpos[kr]];
+      f[p] = aik;
+      // merge the upper part of row kr into the rest of row i
+      i64 l = p + 1;
+      for (i64 q = dpos[kr] + 1; q < indptr[kr + 1] && l < e; ++q) {
+        const I j = indices[q];
+        while (l < e && indices[l] < j) ++l;
+        if (l < e && indices[l] == j) f[l] -= aik * f[q];
+      }
+    }
+    if (bad == n && bad_pivot(f[d])) bad = i;
+  }
+  return bad;
+}
+
+static i64 ilu0_factor(uintptr_t indptr, uintptr_t indices, uintptr_t f,
+                       uintptr_t dpos, i64 n, int dtype, int idx_dtype) {
+  i64 r = n;
+  DISPATCH_VAL(dtype, DISPATCH_IDX(idx_dtype, (
+      r = ilu0_factor_impl<scalar_t, index_t>(
+          reinterpret_cast<const i64*>(indptr),
+          reinterpret_cast<const index_t*>(indices),
+          reinterpret_cast<scalar_t*>(f),
+          reinterpret_cast<const i64*>(dpos), n))));
+  return r;
+}
+
 PYBIND11_MODULE(_cpu_kernels, m) {
+  m.def("level_schedule", &level_schedule);
+  m.def("sptrsv", &sptrsv);
+  m.def("ilu0_factor", &ilu0_factor);
   m.doc() = "legate_sparse CPU/OpenMP kernels";
   m.def("spmv", &spmv, py::arg("indptr"), py::arg("indices"), py::arg("vals"),
         py::arg("x"), py::arg("y"), py::arg("n_rows"), py::arg("dtype"),

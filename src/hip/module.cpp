@@ -129,6 +129,15 @@ int ls_block_update_grid_cap();
 int ls_block_update_per_block();
 int ls_block_residual_grid_cap();
 int ls_block_residual_per_block();
+void ls_sptrsv(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+               uintptr_t, uintptr_t, i64, int, i64, i64, uintptr_t, i64,
+               uintptr_t, i64, bool, bool, int, int, int, uintptr_t);
+void ls_ilu0_factor(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                    uintptr_t, uintptr_t, i64, i64, uintptr_t, i64, uintptr_t,
+                    i64, bool, int, int, int, uintptr_t);
+int ls_sptrsv_kmax();
+int ls_sptrsv_chain_rows();
+int ls_sptrsv_grid_cap();
 
 PYBIND11_MODULE(_hip_kernels, m) {
   m.doc() = "legate_sparse gfx950 HIP kernels";
@@ -205,6 +214,12 @@ PYBIND11_MODULE(_hip_kernels, m) {
   m.attr("BLOCK_UPDATE_PER_BLOCK") = ls_block_update_per_block();
   m.attr("BLOCK_RESIDUAL_GRID_CAP") = ls_block_residual_grid_cap();
   m.attr("BLOCK_RESIDUAL_PER_BLOCK") = ls_block_residual_per_block();
+  // level-scheduled triangular solve and ILU(0) (sptrsv.hip)
+  m.def("sptrsv", &ls_sptrsv);
+  m.def("ilu0_factor", &ls_ilu0_factor);
+  m.attr("SPTRSV_KMAX") = ls_sptrsv_kmax();
+  m.attr("SPTRSV_CHAIN_ROWS") = ls_sptrsv_chain_rows();
+  m.attr("SPTRSV_GRID_CAP") = ls_sptrsv_grid_cap();
   m.attr("arch") = "gfx950";
   m.attr("spgemm_lds_bins") = py::make_tuple(48, 128, 1024, 4096);
 }
