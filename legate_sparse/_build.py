@@ -63,6 +63,7 @@ HIP_SOURCES = [
     os.path.join(SRC_DIR, "hip", "block_ops.hip"),
     os.path.join(SRC_DIR, "hip", "segsort.hip"),
     os.path.join(SRC_DIR, "hip", "sptrsv.hip"),
+    os.path.join(SRC_DIR, "hip", "fsai.hip"),
 ]
 
 

@@ -1,6 +1,7 @@
 # SPDX-License-Identifier: Apache-2.0
 """Iterative solvers: CG, GMRES, BiCGSTAB, LOBPCG, LinearOperator; the
-sparse triangular solve and the ILU(0) preconditioner.
+sparse triangular solve and the ILU(0) preconditioner; the
+FSAI preconditioner.
 
 Counterpart of the reference's ``legate_sparse/linalg.py`` (linalg.py:85-668).
 The key property preserved is the *async solver pipeline* (SURVEY §3.4):
@@ -1381,3 +1382,285 @@ def ilu0(A) -> ILU0:
     ``RuntimeError`` naming the global row for a zero or non-finite pivot.
     See :class:`ILU0`."""
     return ILU0(A)
+
+
+# ---------------------------------------------------------------------------
+# Factorised sparse approximate inverse (docs/DESIGN.md §18)
+# ---------------------------------------------------------------------------
+def _row_ids(indptr: torch.Tensor, lo: int) -> torch.Tensor:
+    """Global row number of every stored entry of a local CSR."""
+    n = int(indptr.numel()) - 1
+    return torch.repeat_interleave(
+        torch.arange(lo, lo + n, device=indptr.device),
+        indptr[1:] - indptr[:-1])
+
+
+def _lower_triangle(indptr, indices, lo):
+    """(indptr, indices) of the entries with ``col <= row``."""
+    n = int(indptr.numel()) - 1
+    row = _row_ids(indptr, lo)
+    keep = indices.long() <= row
+    cnt = torch.bincount(row[keep] - lo, minlength=n)
+    ip = torch.zeros(n + 1, dtype=torch.int64, device=indptr.device)
+    torch.cumsum(cnt, 0, out=ip[1:])
+    return ip, indices[keep].contiguous()
+
+
+def _canonical_csr(A):
+    """``A`` itself when its rows are sorted and duplicate-free, else a copy
+    with the duplicates summed."""
+    from .csr import _assemble_local_rows, csr_array
+
+    if A.has_canonical_format:
+        return A
+    ip, ix, dv = _assemble_local_rows(
+        _row_ids(A._indptr, 0), A._indices.long(), A._data,
+        A._row_hi - A._row_lo, A.shape[1], dedup=True)
+    Ac = csr_array.__new__(csr_array)
+    Ac._init_local(ip, ix, dv.contiguous(), A.shape)
+    return Ac
+
+
+class FSAI(LinearOperator):
+    """Factorised sparse approximate inverse preconditioner
+    (Kolotilina-Yeremin) of a Hermitian positive definite ``A = L L^H``: a
+    sparse lower-triangular ``G ~ L^-1`` on a prescribed pattern, applied as
+    ``M = G^H G`` with two sparse matrix-vector products.
+
+    Row i of G on its pattern ``P_i`` (sorted, last entry i) is the last
+    row of ``C^-1`` where ``A[P_i, P_i] = C C^H``: ``diag(G A G^H) = 1``,
+    G's diagonal is real and positive, and with the full lower-triangular
+    pattern ``G = inv(cholesky(A))``.  Only the entries of A with
+    ``col <= row`` are read; the upper triangle is never touched.
+
+    ``G`` and ``GH`` are ordinary distributed csr_arrays, so the apply is
+    exact at every world size.  After construction ``matvec`` and ``matmat``
+    read nothing back from the device.  A pattern row holds at most
+    ``FSAI_MAX_ROW`` = 32 entries.
+    """
+
+    def __init__(self, A, pattern=None, _impl: str = "native"):
+        from .csr import csr_array
+
+        if not isinstance(A, csr_array):
+            A = csr_array(A)
+        n = A.shape[0]
+        if A.shape[0] != A.shape[1]:
+            raise ValueError(f"fsai needs a square matrix, got {A.shape}")
+        super().__init__(A.shape, dtype=A.dtype)
+        self._impl = _impl
+        lo, hi = A._row_lo, A._row_hi
+        self._lo, self._hi = lo, hi
+        ln = hi - lo
+        dev = A._data.device
+        A = _canonical_csr(A)
+        self._src = (A._indptr, A._indices)
+
+        # -- pattern ------------------------------------------------------
+        if pattern is None:
+            pattern = 1
+        if isinstance(pattern, csr_array):
+            if tuple(pattern.shape) != tuple(A.shape):
+                raise ValueError(f"pattern has shape {pattern.shape}, A has "
+                                 f"{A.shape}")
+            src_ip, src_ix = pattern._indptr, pattern._indices
+        elif isinstance(pattern, (int, np.integer)) \
+                and not isinstance(pattern, bool):
+            if pattern < 1:
+                raise ValueError("pattern power must be at least 1")
+            # unit values on |A|'s pattern: every product entry is a
+            # positive count, nothing cancels or overflows
+            rdt = torch.float32 if A._data.dtype in (
+                torch.float32, torch.complex64) else torch.float64
+            B = A._with_data(torch.ones(A._data.numel(), dtype=rdt,
+                                        device=dev))
+            Q = B
+            for _ in range(int(pattern) - 1):
+                Q = Q.dot(B)
+            src_ip, src_ix = Q._indptr, Q._indices
+        else:
+            raise TypeError("pattern must be None, an int power or a "
+                            "csr_array")
+        p_ip, p_ix = _lower_triangle(src_ip, src_ix, lo)
+
+        # -- checks, the same decision on every rank (§13.4) ----------------
+        plen = p_ip[1:] - p_ip[:-1]
+        rows = torch.arange(lo, hi, device=dev)
+        if p_ix.numel():
+            last = p_ix[(p_ip[1:] - 1).clamp(min=0)].long()
+            nodiag = (plen < 1) | (last != rows)
+        else:
+            nodiag = torch.ones(ln, dtype=torch.bool, device=dev)
+        long_row = torch.where(plen > ops.FSAI_MAX_ROW, rows,
+                               torch.full_like(rows, n))
+        verdict = torch.stack([
+            nodiag.any().to(torch.int64) if ln else rows.new_zeros(()),
+            n - (long_row.min() if ln else rows.new_full((), n)),
+            plen.max() if ln else rows.new_zeros(())]).to(runtime.device)
+        if runtime.world_size > 1:
+            comm.allreduce_(verdict, op="max")
+        missing, long_at, max_row = verdict.cpu().tolist()
+        if missing:
+            raise ValueError("fsai: every pattern row needs its diagonal "
+                             "entry")
+        if long_at:
+            raise ValueError(
+                f"fsai: pattern row {n - long_at} has more than "
+                f"FSAI_MAX_ROW = {ops.FSAI_MAX_ROW} entries")
+        # the global longest row picks the kernel on every rank alike
+        self._max_row = max(int(max_row), 1)
+
+        self._flag = torch.empty(1, dtype=torch.int32, device=dev)
+        self.G = csr_array.__new__(csr_array)
+        self.G._init_local(p_ip, p_ix, torch.zeros(
+            p_ix.numel(), dtype=A._data.dtype, device=dev), A.shape)
+        self.G.data = self._rows(A, validate=True)
+        self.GH = self.G.conj().transpose()
+        self._gh_plan = None
+        self._tmp = torch.empty(ln, dtype=A._data.dtype, device=dev)
+
+    # -- setup ----------------------------------------------------------------
+    def _rows(self, A, validate: bool) -> torch.Tensor:
+        """G's values from A's: gather the window of A's rows this rank's
+        pattern names (a collective above world size 1), one kernel launch,
+        one host read of the pivot flag."""
+        from .csr import _gather_B_window
+
+        w_ip, w_ix, w_dv, w_off = _gather_B_window(self.G, A)
+        vals = ops.fsai_rows(self.G._indptr, self.G._indices, w_ip, w_ix,
+                             w_dv, w_off, self._lo, self._flag,
+                             self._max_row, _impl=self._impl,
+                             _validate=validate)
+        bad = int(self._flag.item())
+        n = self.shape[0]
+        row = torch.tensor([self._lo + bad if bad < self._hi - self._lo
+                            else n], dtype=torch.int64,
+                           device=runtime.device)
+        if runtime.world_size > 1:
+            comm.allreduce_(row, op="min")
+        row = int(row.item())
+        if row < n:
+            raise RuntimeError(
+                f"fsai: A is not positive definite at row {row}")
+        return vals
+
+    def _gh_values(self, gvals: torch.Tensor) -> torch.Tensor:
+        """GH's values from G's through a stored permutation, built at the
+        first ``refactor`` and reused, so later ones move values only.
+
+        The permutation is read off ``csr_array.transpose`` itself: a copy
+        of G whose values are its own local entry numbers is transposed
+        once, which tells every entry of GH the entry of G it came from;
+        the rank that holds it is the owner of GH's column (G's row) under
+        the row partition.  Nothing here depends on HOW transpose orders
+        its output.  Above world size 1 each rank then asks the owners for
+        the entries it needs (one all-to-allv of index lists, once), and
+        every call answers with one all-to-allv of values."""
+        ws = runtime.world_size
+        if self._gh_plan is None:
+            nnz = int(self.G._data.numel())
+            # entry numbers are exact in float64 (nnz < 2**53)
+            ids = self.G._with_data(torch.arange(
+                nnz, dtype=torch.float64, device=self.G._data.device))
+            T = ids.transpose()
+            if not (T._indptr.shape == self.GH._indptr.shape
+                    and torch.equal(T._indptr, self.GH._indptr)
+                    and torch.equal(T._indices, self.GH._indices)):
+                raise RuntimeError("fsai: transpose gave GH another layout")
+            src_idx = T._data.long()
+            if ws == 1:
+                self._gh_plan = (src_idx, None, None, None)
+            else:
+                part = runtime.partition(self.shape[0])
+                src = torch.clamp(torch.div(
+                    T._indices.long(), max(part.chunk, 1),
+                    rounding_mode="floor"), max=ws - 1)
+                # received values arrive grouped by source rank, each group
+                # in the order of the request sent to that rank
+                order = torch.argsort(src, stable=True)
+                want = torch.bincount(src.cpu(), minlength=ws).tolist()
+                asked = comm.alltoallv(
+                    list(torch.split(src_idx[order], want)))
+                give = [int(t.numel()) for t in asked]
+                self._gh_plan = (None, torch.cat(asked), give, order)
+        perm, send_idx, give, order = self._gh_plan
+        if perm is not None:
+            v = gvals[perm]
+        else:
+            got = torch.cat(comm.alltoallv(
+                list(torch.split(gvals[send_idx], give))))
+            v = torch.empty_like(got)
+            v[order] = got
+        return torch.conj(v).resolve_conj().contiguous()
+
+    def refactor(self, A2) -> "FSAI":
+        """New values on the SAME sparsity pattern: the pattern
+        construction and the argument checks are skipped, and ``G`` and
+        ``GH`` stay the same objects, so their cached SpMV plans survive;
+        GH's values follow G's through a stored permutation.  A
+        non-canonical ``A2`` is summed on a copy first, as in ``fsai``.
+        ``ValueError`` for another pattern."""
+        same = (tuple(A2.shape) == self.shape
+                and getattr(A2, "format", None) == "csr"
+                and hasattr(A2, "_indptr"))
+        if same:
+            A2 = _canonical_csr(A2)
+            ip, ix = self._src
+            same = (A2._indptr is ip and A2._indices is ix) or (
+                A2._indptr.shape == ip.shape and A2._indices.shape == ix.shape
+                and torch.equal(A2._indptr, ip)
+                and torch.equal(A2._indices.long(), ix.long()))
+        if runtime.world_size > 1:
+            flag = torch.tensor([0 if same else 1], dtype=torch.int64,
+                                device=runtime.device)
+            comm.allreduce_(flag, op="max")
+            same = not bool(flag.item())
+        if not same:
+            raise ValueError("refactor needs a csr_array with the sparsity "
+                             "pattern of the matrix fsai was built from")
+        want = to_torch_dtype(self.dtype)
+        if A2._data.dtype != want:
+            A2 = A2.astype(self.dtype)
+        vals = self._rows(A2, validate=False)
+        # through the data setter: it marks value-bound caches stale
+        self.G.data = vals
+        self.GH.data = self._gh_values(vals)
+        return self
+
+    # -- apply ------------------------------------------------------------------
+    def matvec(self, r, out=None):
+        """``G^H (G r)``: two SpMVs, the intermediate in a buffer allocated
+        at construction."""
+        x = _to_local_vec(r, self.shape[0], self.dtype, self._tmp.device)
+        if out is not None:
+            out = _plain(out)
+        self.G.dot(x, out=self._tmp)
+        y = self.GH.dot(self._tmp, out=out)
+        return out if out is not None else _plain(y)
+
+    def matmat(self, R):
+        """``G^H (G R)`` for an (n, k) block through the SpMM kernels."""
+        if getattr(R, "ndim", None) != 2:
+            raise ValueError("expected a 2-D block of column vectors")
+        return _plain(self.GH.matmat(_plain(self.G.matmat(R))))
+
+    # the operator is Hermitian
+    rmatvec = matvec
+    rmatmat = matmat
+
+
+def fsai(A, pattern=None) -> FSAI:
+    """FSAI preconditioner of a square Hermitian positive definite
+    csr_array in canonical format (duplicates are summed on a copy first),
+    as a ``LinearOperator`` any solver here takes as ``M=``::
+
+        M = linalg.fsai(A); x, it = linalg.cg(A, b, M=M)
+
+    ``pattern``: ``None`` or an int ``p >= 1`` for the lower triangle of
+    the pattern of ``|A|^p`` (``p - 1`` SpGEMMs), or a csr_array of A's
+    shape whose lower triangle is taken.  Only the entries of A with
+    ``col <= row`` are read.  ``ValueError`` for a pattern row without its
+    diagonal or with more than ``FSAI_MAX_ROW`` = 32 entries (before any
+    kernel runs), ``RuntimeError`` naming the global row where A is not
+    positive definite.  See :class:`FSAI`."""
+    return FSAI(A, pattern)

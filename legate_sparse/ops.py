@@ -1728,3 +1728,198 @@ def _ilu0_factor_torch(indptr, indices, F, dpos, sched, flag):
                         torch.full((), _I32_MAX, device=dev)).min()
     flag.copy_(first.to(torch.int32).reshape(1))
     return F
+
+
+# ---------------------------------------------------------------------------
+# FSAI setup (docs/DESIGN.md §18): row i of G on its sorted pattern P_i
+# (last entry i) is the last row of C^{-1}, A[P_i, P_i] = C C^H.  Rows are
+# independent: one launch, one sub-wave per row.
+# ---------------------------------------------------------------------------
+FSAI_MAX_ROW = 32
+# longest pattern row the 8-lane mapping takes (the extension exports the
+# same numbers; tests compare them)
+FSAI_NARROW = 8
+FSAI_GRID_CAP = 4096
+# blocks the torch arm factors at a time: chunk * max_row**2 entries
+_FSAI_TORCH_CHUNK_ENTRIES = 1 << 24
+
+
+def _fsai_check(p_indptr, p_indices, w_indptr, w_indices, w_vals,
+                row_offset, row_lo, flag, max_row, out, validate):
+    if w_vals.dtype not in _DTYPE_CODE or w_indices.dtype not in _IDX_CODE:
+        raise ValueError("fsai_rows: unsupported value or index dtype")
+    dev = w_vals.device
+    n = int(p_indptr.numel()) - 1
+    n_win = int(w_indptr.numel()) - 1
+    if n < 0 or n_win < 0:
+        raise ValueError("fsai_rows: indptr arrays need at least one entry")
+    for t, dt in ((p_indptr, torch.int64), (w_indptr, torch.int64),
+                  (p_indices, w_indices.dtype), (w_indices, w_indices.dtype),
+                  (w_vals, w_vals.dtype), (out, w_vals.dtype)):
+        if (t.dtype != dt or t.ndim != 1 or t.device != dev
+                or not t.is_contiguous()):
+            raise ValueError("fsai_rows: needs contiguous 1-D arrays on one "
+                             "device, int64 indptr, one index dtype and one "
+                             "value dtype")
+    if w_vals.numel() != w_indices.numel() \
+            or out.numel() != p_indices.numel():
+        raise ValueError("fsai_rows: values do not match their indices")
+    if (flag.dtype != torch.int32 or flag.numel() != 1
+            or flag.device != dev):
+        raise ValueError("fsai_rows: flag is one int32 on the matrix's "
+                         "device")
+    if not 1 <= int(max_row) <= FSAI_MAX_ROW:
+        raise ValueError(f"fsai_rows: longest row {max_row} outside "
+                         f"[1, FSAI_MAX_ROW = {FSAI_MAX_ROW}]")
+    if n > _I32_MAX:
+        raise ValueError("fsai_rows: too many local rows")
+    if not validate or n == 0:
+        return n, n_win
+    # the kernels take raw pointers: everything they index is checked here
+    # (index arithmetic on the device, two host reads: the indptr arrays
+    # first, because the index checks below rely on them)
+    plen = p_indptr[1:] - p_indptr[:-1]
+    wlen = w_indptr[1:] - w_indptr[:-1]
+    pnnz, wnnz = int(p_indices.numel()), int(w_indices.numel())
+    bad = [p_indptr[0] != 0, p_indptr[-1] != pnnz, (plen < 1).any(),
+           (plen > int(max_row)).any(), w_indptr[0] < 0,
+           w_indptr[-1] > wnnz, (wlen < 0).any()]
+    shape_bad = torch.stack([b.reshape(()) for b in bad]).cpu().tolist()
+    if any(shape_bad[:4]):
+        raise ValueError("fsai_rows: the pattern's indptr is inconsistent, a "
+                         "row is empty or a row is longer than max_row")
+    if any(shape_bad[4:]):
+        raise ValueError("fsai_rows: the window's indptr is inconsistent")
+    col = p_indices.long()
+    row_of = torch.repeat_interleave(torch.arange(n, device=dev), plen)
+    inc = torch.ones(pnnz, dtype=torch.bool, device=dev)
+    inc[1:] = (col[1:] > col[:-1]) | (row_of[1:] != row_of[:-1])
+    last = col[p_indptr[1:] - 1]
+    lo, hi = int(row_offset), int(row_offset) + n_win
+    wcol_bad = (w_indices < 0).any() if wnnz else inc.new_zeros(())
+    checks = torch.stack([
+        (~inc).any(),
+        (last != torch.arange(n, device=dev) + int(row_lo)).any(),
+        ((col < lo) | (col >= hi)).any(), wcol_bad]).cpu().tolist()
+    if checks[0]:
+        raise ValueError("fsai_rows: pattern rows must be sorted and free "
+                         "of duplicates")
+    if checks[1]:
+        raise ValueError("fsai_rows: every pattern row must end with its "
+                         "diagonal entry")
+    if checks[2]:
+        raise ValueError(f"fsai_rows: the window rows [{lo}, {hi}) do not "
+                         f"cover the pattern's columns")
+    if checks[3]:
+        raise ValueError("fsai_rows: negative window column")
+    return n, n_win
+
+
+def fsai_rows(p_indptr: torch.Tensor, p_indices: torch.Tensor,
+              w_indptr: torch.Tensor, w_indices: torch.Tensor,
+              w_vals: torch.Tensor, row_offset: int, row_lo: int,
+              flag: torch.Tensor, max_row: int,
+              out: Optional[torch.Tensor] = None, _impl: str = "native",
+              _grid_cap=None, _validate: bool = True) -> torch.Tensor:
+    """Values of the FSAI factor G in the pattern's layout.
+
+    ``p_indptr`` / ``p_indices``: the pattern of this rank's rows, GLOBAL
+    sorted columns, the last entry of local row r being its diagonal
+    ``row_lo + r``.  ``w_*``: a CSR window of the Hermitian positive
+    definite matrix holding its rows ``[row_offset, row_offset + n_win)``
+    with global sorted columns; it must cover every pattern column.  Only
+    window entries with ``col <= row`` are read.  ``max_row`` bounds the
+    longest pattern row (<= FSAI_MAX_ROW) and picks the sub-wave width: 8
+    lanes up to FSAI_NARROW, else 32.  ``flag`` (one int32 on the device)
+    receives the smallest local row with a pivot that is not positive and
+    finite, or 2**31 - 1; nothing is read back from the kernel here.
+    ``_validate=False`` skips the argument checks that read the index
+    arrays (the caller vouches for arrays that passed them before).
+    Bit-identical from run to run."""
+    if _impl not in _SPTRSV_IMPLS:
+        raise ValueError(f"_impl must be one of {_SPTRSV_IMPLS}")
+    if out is None:
+        out = torch.empty(p_indices.numel(), dtype=w_vals.dtype,
+                          device=w_vals.device)
+    n, n_win = _fsai_check(p_indptr, p_indices, w_indptr, w_indices, w_vals,
+                           row_offset, row_lo, flag, max_row, out, _validate)
+    if _grid_cap is not None and not 1 <= int(_grid_cap) <= FSAI_GRID_CAP:
+        raise ValueError(f"_grid_cap outside [1, {FSAI_GRID_CAP}]")
+    cap = 0 if _grid_cap is None else int(_grid_cap)
+    flag.fill_(_I32_MAX)
+    if n == 0:
+        return out
+    if _impl == "torch" or (out.is_cuda and settings.force_cpu_fallback):
+        return _fsai_rows_torch(p_indptr, p_indices, w_indptr, w_indices,
+                                w_vals, int(row_offset), flag, int(max_row),
+                                out)
+    if out.is_cuda:
+        ext = _cext.require_hip()
+        ext.fsai_rows(p_indptr.data_ptr(), p_indices.data_ptr(),
+                      p_indices.numel(), w_indptr.data_ptr(),
+                      w_indices.data_ptr(), w_vals.data_ptr(), n_win,
+                      w_indices.numel(), int(row_offset), int(row_lo), n,
+                      out.data_ptr(), flag.data_ptr(), int(max_row), cap,
+                      _code(w_vals), _icode(w_indices), _stream())
+        return out
+    bad = _cext.require_cpu().fsai_rows(
+        p_indptr.data_ptr(), p_indices.data_ptr(), w_indptr.data_ptr(),
+        w_indices.data_ptr(), w_vals.data_ptr(), n_win, int(row_offset),
+        int(row_lo), n, out.data_ptr(), _code(w_vals), _icode(w_indices))
+    if bad < n:
+        flag.fill_(int(bad))
+    return out
+
+
+def _fsai_rows_torch(p_indptr, p_indices, w_indptr, w_indices, w_vals,
+                     row_offset, flag, max_row, out):
+    """Batched dense formulation: every row's block padded to ``max_row``
+    with identity, S looked up by searchsorted on row * K + col keys of the
+    window, batched Cholesky and one triangular solve per block."""
+    dev = out.device
+    n = int(p_indptr.numel()) - 1
+    n_win = int(w_indptr.numel()) - 1
+    pnnz, wnnz = int(p_indices.numel()), int(w_indices.numel())
+    Mx = int(max_row)
+    pcol = p_indices.long()
+    wcol = w_indices.long()
+    K = int(max(int(pcol.max()), int(wcol.max()) if wnnz else 0)) + 1
+    wrow = torch.repeat_interleave(
+        torch.arange(n_win, device=dev) + row_offset,
+        w_indptr[1:] - w_indptr[:-1])
+    wkeys = wrow * K + wcol
+    plen = p_indptr[1:] - p_indptr[:-1]
+    ar = torch.arange(Mx, device=dev)
+    tril = ar[:, None] >= ar[None, :]
+    eye = torch.eye(Mx, dtype=out.dtype, device=dev)
+    first = torch.full((), _I32_MAX, dtype=torch.int64, device=dev)
+    chunk = max(1, _FSAI_TORCH_CHUNK_ENTRIES // (Mx * Mx))
+    for r0 in range(0, n, chunk):
+        r1 = min(n, r0 + chunk)
+        ln = plen[r0:r1]
+        valid = ar[None, :] < ln[:, None]
+        pos = (p_indptr[r0:r1, None] + ar[None, :]).clamp(max=pnnz - 1)
+        cols = torch.where(valid, pcol[pos], torch.zeros_like(pos))
+        both = valid[:, :, None] & valid[:, None, :] & tril[None]
+        tk = cols[:, :, None] * K + cols[:, None, :]
+        if wnnz:
+            loc = torch.searchsorted(wkeys, tk.reshape(-1)).reshape(
+                tk.shape).clamp(max=wnnz - 1)
+            hit = both & (wkeys[loc] == tk)
+            S = torch.where(hit, w_vals[loc], torch.zeros_like(w_vals[:1]))
+        else:
+            S = torch.zeros(tk.shape, dtype=out.dtype, device=dev)
+        dg = torch.diagonal(S, dim1=1, dim2=2)
+        S = S + S.mH - torch.diag_embed(dg)
+        S = S + eye[None] * (~valid)[:, :, None].to(out.dtype)
+        L, info = torch.linalg.cholesky_ex(S)
+        E = (ar[None, :] == (ln[:, None] - 1)).to(out.dtype).unsqueeze(-1)
+        w = torch.linalg.solve_triangular(L.mH, E, upper=True)[:, :, 0]
+        out[p_indptr[r0]:p_indptr[r1]] = w.conj()[valid]
+        wr = torch.view_as_real(w) if w.is_complex() else w.unsqueeze(-1)
+        bad = (info != 0) | ~torch.isfinite(wr).all(dim=-1).all(dim=-1)
+        rows = torch.arange(r0, r1, device=dev)
+        first = torch.minimum(first, torch.where(
+            bad, rows, torch.full_like(rows, _I32_MAX)).min())
+    flag.copy_(first.to(torch.int32).reshape(1))
+    return out

@@ -332,7 +332,118 @@ static i64 ilu0_factor(uintptr_t indptr, uintptr_t indices, uintptr_t f,
   return r;
 }
 
+// ---------------------------------------------------------------------------
+// FSAI setup (docs/DESIGN.md §18)
+// ---------------------------------------------------------------------------
+#define LS_FSAI_MAX_ROW 32
+
+template <typename T> struct fsai_real { using type = T; };
+template <typename T> struct fsai_real<std::complex<T>> { using type = T; };
+static inline float fs_conj(float v) { return v; }
+static inline double fs_conj(double v) { return v; }
+template <typename T>
+static inline std::complex<T> fs_conj(std::complex<T> v) { return std::conj(v); }
+static inline float fs_re(float v) { return v; }
+static inline double fs_re(double v) { return v; }
+template <typename T>
+static inline T fs_re(std::complex<T> v) { return v.real(); }
+
+// Row r of G on its sorted pattern P (m entries, the last one the diagonal
+// row_lo + r): S = A[P, P] from the entries of A with col <= row (window
+// rows [row_offset, row_offset + n_win)), S = C C^H, C^H w = e_m, row =
+// conj(w).  The same per-row arithmetic and order as fsai.hip.  A pivot
+// that is not positive and finite is replaced by 1; returns the smallest
+// such local row (also for a pattern row the kernel cannot take), or
+// n_local.
+template <typename T, typename I>
+static i64 fsai_rows_impl(const i64* p_indptr, const I* p_indices,
+                          const i64* w_indptr, const I* w_indices,
+                          const T* w_vals, i64 n_win, i64 row_offset,
+                          i64 row_lo, i64 n_local, T* G) {
+  using R = typename fsai_real<T>::type;
+  constexpr int W = LS_FSAI_MAX_ROW;
+  i64 first_bad = n_local;
+#pragma omp parallel for schedule(dynamic, 256) reduction(min : first_bad) \
+    if (n_local > 2048)
+  for (i64 r = 0; r < n_local; ++r) {
+    const i64 ps = p_indptr[r];
+    const i64 m64 = p_indptr[r + 1] - ps;
+    if (m64 < 1 || m64 > W) {
+      first_bad = std::min(first_bad, r);
+      continue;
+    }
+    const int m = (int)m64;
+    T S[W * (W + 1) / 2];
+    i64 P[W];
+    bool bad = false;
+    std::fill(S, S + m * (m + 1) / 2, T(0));
+    for (int a = 0; a < m; ++a) P[a] = (i64)p_indices[ps + a];
+    if (P[m - 1] != row_lo + r) bad = true;
+    for (int a = 0; a < m; ++a) {
+      const i64 pa = P[a], wr = pa - row_offset;
+      if (wr < 0 || wr >= n_win) {
+        bad = true;
+        continue;
+      }
+      for (i64 q = w_indptr[wr]; q < w_indptr[wr + 1]; ++q) {
+        const i64 c = (i64)w_indices[q];
+        if (c > pa) continue;  // the upper triangle is never read
+        const i64* hit = std::lower_bound(P, P + a + 1, c);
+        if (hit != P + a + 1 && *hit == c)
+          S[a * (a + 1) / 2 + (hit - P)] = w_vals[q];
+      }
+    }
+    for (int k = 0; k < m; ++k) {
+      const int rk = k * (k + 1) / 2;
+      T skk = S[rk + k];
+      for (int j = 0; j < k; ++j) skk = skk - S[rk + j] * fs_conj(S[rk + j]);
+      R piv = fs_re(skk);
+      if (!(piv > R(0)) || piv - piv != R(0)) {
+        bad = true;
+        piv = R(1);
+      }
+      const R d = std::sqrt(piv);
+      for (int a = k + 1; a < m; ++a) {
+        const int ra = a * (a + 1) / 2;
+        T s = S[ra + k];
+        for (int j = 0; j < k; ++j) s = s - S[ra + j] * fs_conj(S[rk + j]);
+        S[ra + k] = s / d;
+      }
+      S[rk + k] = T(d);
+    }
+    T acc[W];
+    std::fill(acc, acc + m, T(0));
+    for (int b = m - 1; b >= 0; --b) {
+      const int rb = b * (b + 1) / 2;
+      const T rhs = b == m - 1 ? T(1) : T(0);
+      const T wb = (rhs - acc[b]) / fs_re(S[rb + b]);
+      for (int a = 0; a < b; ++a) acc[a] += fs_conj(S[rb + a]) * wb;
+      G[ps + b] = fs_conj(wb);
+    }
+    if (bad) first_bad = std::min(first_bad, r);
+  }
+  return first_bad;
+}
+
+static i64 fsai_rows(uintptr_t p_indptr, uintptr_t p_indices,
+                     uintptr_t w_indptr, uintptr_t w_indices,
+                     uintptr_t w_vals, i64 n_win, i64 row_offset, i64 row_lo,
+                     i64 n_local, uintptr_t G, int dtype, int idx_dtype) {
+  i64 r = n_local;
+  DISPATCH_VAL(dtype, DISPATCH_IDX(idx_dtype, (
+      r = fsai_rows_impl<scalar_t, index_t>(
+          reinterpret_cast<const i64*>(p_indptr),
+          reinterpret_cast<const index_t*>(p_indices),
+          reinterpret_cast<const i64*>(w_indptr),
+          reinterpret_cast<const index_t*>(w_indices),
+          reinterpret_cast<const scalar_t*>(w_vals), n_win, row_offset,
+          row_lo, n_local, reinterpret_cast<scalar_t*>(G)))));
+  return r;
+}
+
 PYBIND11_MODULE(_cpu_kernels, m) {
+  m.def("fsai_rows", &fsai_rows);
+  m.attr("FSAI_MAX_ROW") = LS_FSAI_MAX_ROW;
   m.def("level_schedule", &level_schedule);
   m.def("sptrsv", &sptrsv);
   m.def("ilu0_factor", &ilu0_factor);

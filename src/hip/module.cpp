@@ -138,6 +138,12 @@ void ls_ilu0_factor(uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
 int ls_sptrsv_kmax();
 int ls_sptrsv_chain_rows();
 int ls_sptrsv_grid_cap();
+void ls_fsai_rows(uintptr_t, uintptr_t, i64, uintptr_t, uintptr_t, uintptr_t,
+                  i64, i64, i64, i64, i64, uintptr_t, uintptr_t, int, int,
+                  int, int, uintptr_t);
+int ls_fsai_max_row();
+int ls_fsai_narrow();
+int ls_fsai_grid_cap();
 
 PYBIND11_MODULE(_hip_kernels, m) {
   m.doc() = "legate_sparse gfx950 HIP kernels";
@@ -220,6 +226,11 @@ PYBIND11_MODULE(_hip_kernels, m) {
   m.attr("SPTRSV_KMAX") = ls_sptrsv_kmax();
   m.attr("SPTRSV_CHAIN_ROWS") = ls_sptrsv_chain_rows();
   m.attr("SPTRSV_GRID_CAP") = ls_sptrsv_grid_cap();
+  // FSAI setup (fsai.hip)
+  m.def("fsai_rows", &ls_fsai_rows);
+  m.attr("FSAI_MAX_ROW") = ls_fsai_max_row();
+  m.attr("FSAI_NARROW") = ls_fsai_narrow();
+  m.attr("FSAI_GRID_CAP") = ls_fsai_grid_cap();
   m.attr("arch") = "gfx950";
   m.attr("spgemm_lds_bins") = py::make_tuple(48, 128, 1024, 4096);
 }
