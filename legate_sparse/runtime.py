@@ -14,11 +14,20 @@ implicitly from Legion's dependence analysis; here it is explicit).
 """
 from __future__ import annotations
 
+import atexit
 import os
 from typing import Optional
 
 import torch
 import torch.distributed as dist
+
+
+def _destroy_process_group() -> None:
+    try:
+        if dist.is_initialized():
+            dist.destroy_process_group()
+    except Exception:  # teardown must never turn a finished run into a failure
+        pass
 
 
 def _ceil_div(a: int, b: int) -> int:
@@ -86,6 +95,12 @@ class Runtime:
         if env_world > 1 and not dist.is_initialized():
             backend = "nccl" if torch.cuda.is_available() else "gloo"
             dist.init_process_group(backend=backend)
+            # a group this runtime created is torn down before the
+            # interpreter finalizes: a process that exits with the
+            # backend's worker threads still joinable can abort in static
+            # destruction ("terminate called without an active exception",
+            # seen now and then on one rank of a finished gloo job)
+            atexit.register(_destroy_process_group)
         if dist.is_initialized():
             self._rank = dist.get_rank()
             self._world_size = dist.get_world_size()

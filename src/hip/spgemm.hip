@@ -292,7 +292,9 @@ __global__ __launch_bounds__(LS_THREADS) void spgemm_affine_kernel(
     T* __restrict__ C_vals, i64 n_rows) {
   extern __shared__ char smem_raw[];
   T* acc = reinterpret_cast<T*>(smem_raw);
-  __shared__ int E_s[32];
+  // nE is bounded by the accumulator budget of spgemm_affine_try (51 KB /
+  // (LS_THREADS * sizeof(T))): 51 for 4-byte values
+  __shared__ int E_s[64];
   __shared__ short ps_s[16 * 16];
   if (threadIdx.x < nE) E_s[threadIdx.x] = E[threadIdx.x];
   if (threadIdx.x < ndA * ndB) ps_s[threadIdx.x] = pair_slot[threadIdx.x];
@@ -1201,8 +1203,8 @@ __global__ __launch_bounds__(LS_THREADS) void spgemm_affine_out_kernel(
     const unsigned char* __restrict__ validC,
     const i64* __restrict__ C_ip, I* __restrict__ C_idx,
     T* __restrict__ C_vals, i64 n_rows) {
-  __shared__ int E_s[32];
-  __shared__ int soff_s[33];
+  __shared__ int E_s[64];  // nE <= 51, as in spgemm_affine_kernel
+  __shared__ int soff_s[65];
   __shared__ short sa_s[16 * 16];
   __shared__ short sb_s[16 * 16];
   const int npairs = slot_off[nE];

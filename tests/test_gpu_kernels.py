@@ -69,6 +69,8 @@ def test_gpu_spmv_long_single_row():
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64, np.complex128])
 def test_gpu_spgemm_small_bin(dtype):
+    # 5 per row on both sides: the affine product takes every interior
+    # row; only the boundary rows reach the general path (merge W = 8)
     A = banded_matrix(300, nnz_per_row=5).astype(dtype)
     C = lsp.csr_array(A) @ lsp.csr_array(A)
     tol = 1e-4 if np.dtype(dtype).itemsize <= 8 else 1e-12
@@ -77,7 +79,9 @@ def test_gpu_spgemm_small_bin(dtype):
 
 
 def test_gpu_spgemm_mid_bin():
-    # rows with expansion bound in (128, 1024]: ~30 nnz/row squared
+    # ~30 nnz/row squared: ub in (128, 1024] with a_len <= 32, so every
+    # row runs the merge kernel W = 32, none an LDS-hash bin (those need
+    # a_len > 64; test_gpu_spgemm.py covers them)
     A = banded_matrix(400, nnz_per_row=31)
     C = lsp.csr_array(A) @ lsp.csr_array(A)
     np.testing.assert_allclose(to_np(C.todense()), (A @ A).toarray(),
@@ -85,7 +89,7 @@ def test_gpu_spgemm_mid_bin():
 
 
 def test_gpu_spgemm_large_bin():
-    # expansion bound in (1024, 4096]
+    # ub in (1024, 4096] with a_len <= 64: merge kernels W = 32 and W = 64
     A = banded_matrix(600, nnz_per_row=57)
     C = lsp.csr_array(A) @ lsp.csr_array(A)
     np.testing.assert_allclose(to_np(C.todense()), (A @ A).toarray(),
@@ -257,7 +261,9 @@ def test_gpu_rmat_spgemm():
 
 @pytest.mark.parametrize("nnz_per_row", [31, 57])
 def test_gpu_spgemm_complex_big_bins(nnz_per_row):
-    """complex128 takes the reduced-ROWS LDS geometries (cfg1/cfg2)."""
+    """complex128 through the merge kernels (a_len <= 64, ub <= 4096: no
+    row reaches an LDS-hash bin; the reduced complex128 geometries are
+    checked in test_gpu_spgemm.py)."""
     A = banded_matrix(500, nnz_per_row=nnz_per_row).astype(np.complex128)
     A = A + 1j * banded_matrix(500, nnz_per_row=nnz_per_row, seed=9)
     A = A.tocsr()
@@ -298,8 +304,10 @@ def test_gpu_jacobi_update():
 
 
 def test_gpu_spgemm_deterministic():
-    """Merge/LDS bins must give bit-identical results across runs
-    (binning order is nondeterministic but per-row outputs are not)."""
+    """The affine product and the merge bins (the boundary rows here) must
+    give bit-identical results across runs (binning order is
+    nondeterministic but per-row outputs are not).  No row reaches a hash
+    bin, which accumulates with atomics and promises no such thing."""
     A = banded_matrix(2000, nnz_per_row=9, seed=31)
     La = lsp.csr_array(A)
     C1 = La @ La
@@ -635,7 +643,9 @@ def test_spgemm_affine_complex():
 @pytest.mark.gpu
 def test_spgemm_segsort_parity():
     """rocPRIM segmented postsort vs the torch composite on a power-law
-    product (hub rows exercise the probed global bins)."""
+    product.  With n_cols = 8192 every hub row gets an identity table, so
+    neither run sorts anything here; the two post-sorts are compared on
+    probed rows in test_gpu_spgemm.py."""
     import os as _os
     from legate_sparse.gallery import rmat
     A = rmat(13, edge_factor=24, seed=3)
